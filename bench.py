@@ -1,6 +1,7 @@
 """bench.py -- imagined frames/s of DIAMOND's imagined-rollout hot path on MI355X.
 
     python bench.py --gpus 1 --steps K --warmup W                      (BASELINE configs[1], the headline metric)
+    python bench.py --gpus 1 --steps K --warmup W --full               (the same + roofline, exact fp32, `also`, CPU baseline)
     python bench.py --config 3 --steps 1 --warmup 1                    (configs[3]: 50-step Heun sampler)
     python bench.py --config 4 --steps 2 --warmup 1                    (configs[4]: 256x256, attention, 8 envs per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -13,7 +14,13 @@ bookkeeping/resets) + loss.backward() + gradient all-reduce (N > 1) + clip_grad_
 Default workload = BASELINE.json configs[1]: Breakout-shaped 64x64x3 frames, batch 256 per GPU, horizon 15,
 3 Euler denoising steps, synthetic weights/inputs.  value = B_global * 15 / (max-over-ranks seconds per step).
 
-Extra objects on the JSON line: `roofline` for the dominant kernel (found by measured time over EVERY C-ABI launch:
+A plain run does only what the headline needs: set up, `--warmup` untimed windows, `--steps` timed windows, the outputs of the
+last timed window if `--dump-outputs DIR` is given (DIR/<name>.npy: what ActorCritic.forward() hands its caller -- loss, metrics,
+the rollout (a seeded sample of its frames) -- and the actor-critic parameters the step's AdamW left; float32, the sampled rows /
+indices float64, <= 64 MB in all), and the JSON line.  `--full` adds the extra objects below (configs[1], [3] and [4];
+`--no-roofline` etc. switch single ones off).
+
+Extra objects on the JSON line (`--full`): `roofline` for the dominant kernel (found by measured time over EVERY C-ABI launch:
 HIP events around each one in a dedicated instrumented window after the timed region), `exact_fp32` = the same window
 with every convolution on the exact-fp32 MFMA kernels (configs[1] only), `also` = what else fits one GPU, measured after the
 timed region (configs[3], configs[4], the B = 1 latency mode, the denoiser training step, and configs[1] WITHOUT the end-logit
@@ -461,6 +468,73 @@ def stagger_episodes(env, horizon):
         env.ep_len = (torch.arange(env.num_envs) % horizon).to(env.ep_len.device)
 
 
+class OutputTap:
+    """--dump-outputs: what ActorCritic.forward() hands its caller in ONE step -- the rollout its env loop yields and the loss with
+    its metrics -- kept detached, each window's record replacing the one before; installed ahead of the warm-up windows (the timed
+    loop is the same code with or without it, and the memory the record holds is already in use while the windows warm up), removed
+    after the timed ones."""
+
+    ROLLOUT = ("obs", "act", "rew", "end", "trunc", "logits_act", "val", "val_bootstrap")
+
+    def __init__(self, ac):
+        self.ac, self.loop, self.forward = ac, ac.env_loop, ac.forward
+        self.rollout = self.loss = self.metrics = None
+        ac.env_loop = self
+        ac.forward = self._forward
+
+    def send(self, num_steps):
+        out = self.loop.send(num_steps)
+        self.rollout = dict(zip(self.ROLLOUT, (t.detach() for t in out[:len(self.ROLLOUT)])))
+        return out
+
+    def _forward(self):
+        loss, metrics = self.forward()
+        self.loss, self.metrics = loss.detach(), metrics
+        return loss, metrics
+
+    def remove(self):
+        self.ac.env_loop = self.loop
+        del self.ac.forward
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, tap, ac, frame_budget=24 * 2 ** 20, param_budget=32 * 2 ** 20):
+    """DIR/<name>.npy of the last timed window: loss, metrics, the rollout (frames: a seeded sample of whole env rows
+    within `frame_budget`) and the actor-critic parameters after the step's AdamW, concatenated in named_parameters() order (a
+    all of them where their float32 values fit `param_budget`, else a seeded sample: float32 values and their float64 positions,
+    12 bytes per sampled parameter, together within `param_budget`).  Returns {name: shape}."""
+    import numpy as np
+
+    arrays = {"loss": tap.loss}
+    arrays.update({f"metric_{k}": v for k, v in tap.metrics.items()})
+    for k, v in tap.rollout.items():
+        if k == "obs":
+            row_bytes = v[0].numel() * 4
+            n = min(v.shape[0], 16, max(1, frame_budget // row_bytes))
+            rows = torch.randperm(v.shape[0], generator=torch.Generator().manual_seed(0))[:n].sort().values
+            arrays["rollout_obs_rows"] = rows
+            arrays["rollout_obs_sample"] = v[rows.to(v.device)]
+        else:
+            arrays[f"rollout_{k}"] = v
+    flat = torch.cat([p.detach().reshape(-1) for _, p in ac.named_parameters()])
+    if flat.numel() * 4 > param_budget:
+        cap = param_budget // 12  # (4 bytes of value + 8 of position per sampled parameter)
+        idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(1))[:cap].sort().values
+        arrays["actor_critic_params_sample_index"] = idx
+        flat = flat[idx.to(flat.device)]
+    arrays["actor_critic_params"] = flat
+    os.makedirs(out_dir, exist_ok=True)
+    # (float32 values; the row / index arrays as float64, exact beyond 2^24)
+    host = {k: np.asarray(v.detach().cpu().numpy(), dtype=np.float64 if k.endswith(("_rows", "_index")) else np.float32)
+            for k, v in arrays.items()}
+    assert sum(a.nbytes for a in host.values()) <= DUMP_LIMIT_BYTES, {k: a.nbytes for k, a in host.items()}
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    return {k: list(a.shape) for k, a in host.items()}
+
+
 def _is_split(key):
     """kernels that run split-fp16 arithmetic (3 f16 MFMAs per algorithmic MAC) are priced against the f16 peak"""
     last_arg_true = key.rstrip(">").rstrip().endswith("true")  # (the SPLIT template argument is the last one: "..., true>" / "..., true>>")
@@ -725,6 +799,12 @@ def main():
     ap.add_argument("--gc", choices=("default", "off", "window"), default="default",
                     help="A/B of python's cyclic garbage collector during the timed region: off = gc.disable(); window = disabled, with one "
                          "gc.collect() between windows (outside no kernel's critical path)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed windows, also measure what the headline does not need: roofline window, exact-fp32 window, "
+                         "`also` (configs[1] only) and the CPU baseline (each can still be switched off by its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed window computed to DIR/<name>.npy (float32 / float64, <= 64 MB: loss, metrics, rollout, "
+                         "actor-critic parameters after the step; seeded samples where larger)")
     ap.add_argument("--no-also", action="store_true", help="skip the extra measurements the default configs[1] line carries (`also`)")
     ap.add_argument("--pmc-calibrate", action="store_true",
                     help="two Heun updates over 256 MiB arrays before the window (tools/pmc_collect.sh: a known byte count for the FETCH_SIZE / "
@@ -743,6 +823,8 @@ def main():
         sys.exit(self_launch(args.gpus, sys.argv[1:], args.dry_launch))
     if args.config in ("latency", "train"):
         assert args.gpus == 1, "--config latency / train are single-GPU measurements"
+        if args.dump_outputs:
+            ap.error("--dump-outputs: configs 1, 3 and 4 only")
         torch.cuda.set_device(0)
         line = latency_line(args) if args.config == "latency" else train_line(args)
         print(json.dumps(line))
@@ -807,6 +889,7 @@ def main():
             print(f"[bench +{time.perf_counter() - t_start:.1f}s] {msg}", file=sys.stderr, flush=True)
 
     progress("setup done")
+    tap = OutputTap(ac) if args.dump_outputs else None
     if args.gc != "default":
         import gc
 
@@ -841,6 +924,12 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
+    if tap is not None:
+        tap.remove()
+        if rank == 0:  # (before anything else runs a window: the parameters are the last timed step's)
+            dumped = dump_outputs(args.dump_outputs, tap, ac)
+            progress(f"outputs of the last timed step written to {args.dump_outputs}: {len(dumped)} arrays")
+        del tap
     if use_dist:
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -916,14 +1005,14 @@ def main():
                                            "bound (roofline), its HBM share is what these FLOPs need"},
     }
 
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # instrumented window (not part of `value`): HIP events around EVERY C-ABI launch (convolutions, attention, linears,
         # fused low-resolution levels, pointwise) on the stream they are launched on; the env replays no captured graph
         # while a profiler is installed (a replay would hide its kernels from the events)
         line["roofline"] = dominant_kernel_roofline(window, nv, args.config, world, custom_flags)
         progress("roofline window done")
 
-    if args.config == 1 and not args.no_exact_fp32 and not custom:
+    if args.full and args.config == 1 and not args.no_exact_fp32 and not custom:
         # the same window with every convolution on the exact-fp32 MFMA kernels (reported next to `value`, never as it)
         saved = (E.WORLD_MODEL_PRECISION, ac_native.AC_PRECISION)
         E.WORLD_MODEL_PRECISION, ac_native.AC_PRECISION = "f32", "f32"
@@ -943,13 +1032,13 @@ def main():
                                        "DIAMOND_AC_PRECISION=f32)"}
         progress("exact-fp32 window done")
 
-    if args.config == 1 and world == 1 and not custom and not args.no_also:
+    if args.full and args.config == 1 and world == 1 and not custom and not args.no_also:
         del agent, ac, window
         torch.cuda.empty_cache()
         line["also"] = also_lines(device, args)
         progress(f"also: {line['also']['seconds']:.1f}s")
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_config4() if args.config == 4 else cpu_baseline(64, allow_reference=args.cpu_baseline_kind == "reference")
         progress("cpu baseline done")
 

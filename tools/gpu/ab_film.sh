@@ -10,7 +10,7 @@ timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider -x > $O/tests.
 for rep in 1 2 3; do
   for f in 1 0; do
     echo "== DIAMOND_BATCH_FILM=$f"
-    DIAMOND_BATCH_FILM=$f timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-exact-fp32 --no-also 2>/dev/null | python -c "
+    DIAMOND_BATCH_FILM=$f timeout 300 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-exact-fp32 --no-also 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); lt = d['roofline']['launch_time_ms']
 print('  window', round(d['value'], 1), 'frames/s', round(d['ms_per_step'], 2), 'ms; linear ms', round(lt.get('linear_mfma_kernel<true>', 0) + lt.get('linear_mfma_kernel<false>', 0), 2))"

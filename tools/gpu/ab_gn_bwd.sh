@@ -14,7 +14,7 @@ for rep in 1 2 3; do
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value'], 3), 'ms/step (graphed);', [(k['kernel'][:28], k['calls'], k['avg_us']) for k in d['roofline']['kernels'][:3]])"
     echo "== window DIAMOND_LIB=$lib"
-    DIAMOND_LIB=$lib timeout 300 python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-exact-fp32 --no-also 2>/dev/null | python -c "
+    DIAMOND_LIB=$lib timeout 300 python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-exact-fp32 --no-also 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('  window', round(d['value'], 1), 'frames/s', round(d['ms_per_step'], 2), 'ms; gn_silu_bwd ms', d['roofline']['launch_time_ms'].get('dmd_gn_silu_bwd'))"
   done

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 for rep in 1 2; do
   for lib in "$@"; do
     echo "== window DIAMOND_LIB=$lib" | tee -a $O/ab_libs.txt
-    DIAMOND_LIB=$lib timeout 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-exact-fp32 --no-also 2>/dev/null | python -c "
+    DIAMOND_LIB=$lib timeout 300 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-exact-fp32 --no-also 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print(round(d['value'], 1), 'frames/s;', r['kernel'], round(1e3 * r['avg_launch_ms'], 1), 'us;', {k: v for k, v in list(r['launch_time_ms'].items())[:9]})" | tee -a $O/ab_libs.txt

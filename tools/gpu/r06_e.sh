@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}; cd $R
 O=$R/gpurun_out/${1:-r06e}; mkdir -p $O
 export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider --durations=8 -x > $O/tests.log 2>&1; echo "pytest rc=$?" | tee -a $O/tests.log; tail -4 $O/tests.log
-timeout 600 python bench.py > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-300 $O/bench_line.json; tail -3 $O/bench.err
+timeout 600 python bench.py --full > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-300 $O/bench_line.json; tail -3 $O/bench.err
 (cd /tmp && rm -rf /tmp/prof_lat && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_lat -o lat -- \
    python $R/bench.py --config latency --steps 100 > $O/latency.log 2>&1
  t=$(find /tmp/prof_lat -name "*kernel_trace.csv" | head -1); k=$(find /tmp/prof_lat -name "*kernel_stats.csv" | head -1)

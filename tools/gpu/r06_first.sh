@@ -15,5 +15,5 @@ for mode in steady_p003 no_ends; do
   [ -n "$t" ] && TRACE_GAPS_DUMP=80 python tools/trace_gaps.py $t 300 400 > $O/${mode}_gaps.txt 2>&1
   tail -1 $O/$mode.log | cut -c1-200
 done
-timeout 500 python bench.py > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-400 $O/bench_line.json
+timeout 500 python bench.py --full > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-400 $O/bench_line.json
 (rocm-smi --showproductname --showclocks --showpower 2>/dev/null | head -40) > $O/box.txt

@@ -19,5 +19,5 @@ for mode in steady_p003 no_ends; do
   [ -n "$t" ] && python tools/trace_gaps.py $t 300 400 > $O/${mode}_gaps.txt 2>&1
   grep '"metric"' $O/$mode.log | cut -c1-160; head -2 $O/${mode}_gaps.txt
 done
-timeout 600 python bench.py > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-300 $O/bench_line.json; tail -3 $O/bench.err
+timeout 600 python bench.py --full > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-300 $O/bench_line.json; tail -3 $O/bench.err
 (rocm-smi --showproductname --showclocks --showpower 2>/dev/null | head -40) > $O/box.txt

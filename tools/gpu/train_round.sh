@@ -16,7 +16,7 @@ for s in "$OLD" "" "$OLD" ""; do
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value'], 1), 'frames/s', d['step_ms'])"
 done 2>&1 | tee $O/ab_window.txt
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_line.json 2> $O/bench.err; echo "bench rc=$?"; tail -2 $O/bench.err
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_line.json 2> $O/bench.err; echo "bench rc=$?"; tail -2 $O/bench.err
 python -c "
 import json; d = json.loads(open('$O/bench_driver_line.json').read().strip().splitlines()[-1])
 print('headline', round(d['value'], 1), 'train', d['also']['train'], 'latency', d['also'].get('latency'))" 2>&1 | cut -c1-600

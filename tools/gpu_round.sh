@@ -14,10 +14,10 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   echo "pytest rc=$?" >> $O/tests.log
   tail -3 $O/tests.log
 fi
-timeout 400 python bench.py > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 600 $O/bench_line.json
+timeout 400 python bench.py --full > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 600 $O/bench_line.json
 if [ "${SKIP_PROFILE:-0}" != "1" ]; then
   (cd /tmp && rm -rf /tmp/prof_$TAG && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -o bench -- \
-     python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-exact-fp32 --no-also > $O/prof_bench.log 2>&1; echo "rocprof rc=$?"
+     python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-exact-fp32 --no-also > $O/prof_bench.log 2>&1; echo "rocprof rc=$?"
    f=$(find /tmp/prof_$TAG -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/bench_kernel_stats.csv && head -12 $f)
   bash tools/pmc_collect.sh > $O/pmc.log 2>&1; echo "pmc rc=$?"
   mkdir -p $O/pmc && cp gpurun_out/pmc/*.json $O/pmc/ 2>/dev/null
@@ -29,8 +29,8 @@ if [ "${SKIP_PROFILE:-0}" != "1" ]; then
   mkdir -p $O/pmc_cfg4 && cp gpurun_out/pmc_cfg4/*.json $O/pmc_cfg4/ 2>/dev/null
 fi
 if [ "${SKIP_CONFIGS:-0}" != "1" ]; then
-  timeout 500 python bench.py --config 4 > $O/bench_config4.json 2> $O/bench_config4.err; echo "cfg4 rc=$?"; tail -c 300 $O/bench_config4.json
-  timeout 400 python bench.py --config 3 --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_config3.json 2> $O/bench_config3.err; echo "cfg3 rc=$?"; tail -c 300 $O/bench_config3.json
+  timeout 500 python bench.py --config 4 --full > $O/bench_config4.json 2> $O/bench_config4.err; echo "cfg4 rc=$?"; tail -c 300 $O/bench_config4.json
+  timeout 400 python bench.py --config 3 --steps 1 --warmup 1 --full --no-cpu-baseline > $O/bench_config3.json 2> $O/bench_config3.err; echo "cfg3 rc=$?"; tail -c 300 $O/bench_config3.json
   timeout 300 python bench.py --config latency > $O/bench_latency.json 2> $O/bench_latency.err; echo "latency rc=$?"; tail -c 400 $O/bench_latency.json
   timeout 300 python bench.py --config train > $O/bench_train.json 2> $O/bench_train.err; echo "train rc=$?"; tail -c 400 $O/bench_train.json
   timeout 300 python bench.py --config train --batch 256 --steps 5 >> $O/bench_train.json 2>> $O/bench_train.err
