@@ -34,12 +34,19 @@ def _maxpool(y: Tensor, valid: Optional[Tuple[int, int]] = None) -> Tuple[Act, T
     n, h, w, c = y.shape
     out = torch.empty(n, h // 2, w // 2, c, device=y.device, dtype=torch.float32)
     arg = torch.empty(n, h // 2, w // 2, c, device=y.device, dtype=torch.uint8)
-    stats = E.new_stats(n, c, 1, y.device) if (c % nv.GN_GROUP == 0 and valid is None) else None
+    # (statistics for every width the grouping rule allows: dmd_gn_stats takes the groups of 32 and the general ones)
+    stats = E.new_stats(n, c, 1, y.device) if (_gn_width_ok(c) and valid is None) else None
     nv.check(nv.lib().dmd_maxpool2(nv.fptr(y), nv.fptr(out), nv.ptr(arg), nv.ptr(stats), n, h, w, c, nv.stream()), "dmd_maxpool2")
     if valid is not None:
         v2 = (valid[0] // 2, valid[1] // 2)
-        return (E.gn_stats(out, v2) if c % nv.GN_GROUP == 0 else Act(out, valid=v2)), arg
+        return (E.gn_stats(out, v2) if _gn_width_ok(c) else Act(out, valid=v2)), arg
     return Act(out, stats, 1 if stats is not None else 0), arg
+
+
+def _gn_width_ok(c: int) -> bool:
+    """mirror of dmd_gn_width_ok (csrc/dmd_common.h): a width whose GroupNorm statistics the kernels form"""
+    g = max(1, c // nv.GN_GROUP)
+    return c % 16 == 0 and c % g == 0 and (c // g) % 4 == 0 and (c % nv.GN_GROUP == 0 or c <= 256)
 
 
 def _maxpool_bwd(dp: Tensor, arg: Tensor) -> Tensor:
@@ -89,12 +96,15 @@ def _pad_channels(t: Tensor, c0: int, c1: int, to: int) -> Tensor:
 
 def _norm_slice(x: Act, spec: NormSpec, c0: int, c1: int, to: int) -> Tuple[Tensor, int, NormSpec]:
     """Statistics and multiplicative / additive parameters of channels [c0, c1) of a normalised source, zero-padded to `to`
-    channels: (partial sums, tiles, spec).  A padded group has sums 0 and parameters 0: its activated value is 0."""
-    g = nv.GN_GROUP
-    assert c0 % g == 0 and (c1 - c0) % g == 0 and to % g == 0 and x.stats is not None, \
+    channels: (partial sums, tiles, spec).  A padded group has sums 0 and parameters 0: its activated value is 0.  Groups of another
+    size than 32 (one group per slice: the general-group kernel instances) carry no padded groups -- the kernel normalises the
+    slice's real channels only."""
+    g = E.gn_group_size(x.C)
+    assert c0 % g == 0 and (c1 - c0) % g == 0 and to % nv.GN_GROUP == 0 and x.stats is not None, \
         f"normalised source of {x.C} channels cut at [{c0}, {c1}): not whole GroupNorm groups"
+    assert g == nv.GN_GROUP or c1 - c0 == g, f"a slice of {c1 - c0} channels of a source in {g}-channel groups: one group per slice"
     stats = x.stats[:, c0 // g:c1 // g]
-    if to != c1 - c0:
+    if to != c1 - c0 and g == nv.GN_GROUP:
         stats = torch.cat([stats, torch.zeros(stats.shape[0], (to - (c1 - c0)) // g, *stats.shape[2:], device=stats.device, dtype=stats.dtype)], 1)
 
     def cut(t: Optional[Tensor], stride: int):
@@ -121,14 +131,17 @@ def _wgrad_tiled(x: Act, prologue: int, spec: Optional[NormSpec], dy: Tensor, ta
     n, h, w, cout = dy.shape
     k = 3 if taps == 9 else 1
     T = 64
+    # a normalised source in groups other than 32 channels: one group per tile (its real channels; dmd_conv2d_wgrad picks the
+    # general-group instance), zero-padded to the 64 -> 64 shape like every other tile
+    step = E.gn_group_size(x.C) if prologue != nv.PROLOGUE_NONE and x.C % nv.GN_GROUP != 0 else T
     if batch is not None:
         dw, db = dw_out, db_out
     else:
         dw = torch.empty(cout, cin_real, k, k, device=dy.device, dtype=torch.float32)
         db = torch.empty(cout, device=dy.device, dtype=torch.float32) if want_bias else None
         c0 = 0
-    for ci0 in range(0, cin_real, T):
-        ci1 = min(cin_real, ci0 + T)
+    for ci0 in range(0, cin_real, step):
+        ci1 = min(cin_real, ci0 + step)
         cw = (ci1 - ci0 + 15) // 16 * 16  # (the source's own padding: conv_in's 15 channels travel as 16)
         if prologue == nv.PROLOGUE_NONE:
             xt, spec_t = Act(_pad_channels(x.t, ci0, min(x.C, ci0 + cw), T), valid=x.valid), None
@@ -202,7 +215,10 @@ def _wgrad(x: Act, prologue: int, spec: Optional[NormSpec], dy: Tensor, taps: in
 
 
 def _gn_bwd_instance(c: int) -> bool:
-    """channel counts dmd_gn_silu_bwd takes (csrc/dmd_backward.hip): 4 ... 256 in powers of two"""
+    """channel counts dmd_gn_silu_bwd takes (csrc/dmd_backward.hip): 4 ... 256 in powers of two, and the general groups (the
+    grouping rule's widths that are not multiples of 32: 48, 80, 144 ...; one workgroup per image)"""
+    if c % nv.GN_GROUP != 0 and c > nv.GN_GROUP:
+        return c <= 256 and _gn_width_ok(c)
     return c % 4 == 0 and c <= 256 and 256 % (c // 4) == 0 and (c % nv.GN_GROUP == 0 or c < nv.GN_GROUP)
 
 

@@ -37,12 +37,16 @@ def conv1x1(cin: int, cout: int) -> nn.Conv2d:
 
 
 def _groups(c: int) -> int:
-    # The reference forms max(1, C // 32) groups of C / groups channels (blocks.py:27,38): groups of exactly 32 whenever C is a
-    # multiple of 32 -- the only case the kernels implement (DMD_GN_GROUP).  Say so where the network is built, not at its first launch.
-    assert c % GN_GROUP_SIZE == 0, (f"normalisation over {c} channels: diamond_amd's kernels normalise in groups of {GN_GROUP_SIZE} channels, "
-                                    f"so every normalised width has to be a multiple of {GN_GROUP_SIZE} (the reference would form "
-                                    f"{max(1, c // GN_GROUP_SIZE)} group(s) of {c / max(1, c // GN_GROUP_SIZE):g} here)")
-    return c // GN_GROUP_SIZE
+    """GroupNorm groups of a normalised width, by the reference's rule (blocks.py:27,38): max(1, C // 32) groups of C / groups
+    channels.  Widths the kernels cannot normalise raise here, where the network is built, not at its first launch."""
+    g = max(1, c // GN_GROUP_SIZE)
+    if c % g != 0:
+        raise ValueError(f"normalisation over {c} channels: the reference's {g} GroupNorm group(s) (max(1, C // {GN_GROUP_SIZE})) do not "
+                         f"divide {c} channels")
+    if c % 16 != 0 or (c // g) % 4 != 0 or (c % GN_GROUP_SIZE != 0 and c > 256):
+        raise ValueError(f"normalisation over {c} channels ({g} group(s) of {c / g:g}): diamond_amd's kernels need C % 16 == 0, groups "
+                         f"of a multiple of 4 channels, and C <= 256 unless C % {GN_GROUP_SIZE} == 0")
+    return g
 
 
 class RunCtx:
@@ -232,6 +236,9 @@ class ResBlock(nn.Module):
     def run(self, ctx: RunCtx, xs: Sequence[Act]) -> Act:
         """xs: the channel-concatenated inputs (never materialised: the conv reads both)."""
         cout = self.conv1.out_channels
+        if E.straddles(xs):
+            # a GroupNorm group of cat(x, skip) spans both sources (widths off the 32-channel grid): normalised as one tensor
+            xs = [E.concat(xs)]
         r, proj = None, None
         if isinstance(self.proj, nn.Identity):
             assert len(xs) == 1

@@ -282,6 +282,8 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const dmd_gn_bwd_para
 // passes are one launch -- pass A's sums stay in LDS, nothing goes through the workspace.  Every sum is formed as the two kernels
 // above form it (T = 1: their "sums over tiles" are one term), every element is computed by the same expression: the results
 // are bit-identical to the two launches (DIAMOND_GN_BWD_FUSED=0 takes those: test hook).
+// ANY: C / 4 need not divide 256 (the general groups: C = 48, 80, 144 ...): the threads behind the last whole pixel row of channel
+// quads (256 - (256 / CQ) * CQ of them) take no pixel; the sums are formed as for ANY = false.
 __global__ __launch_bounds__(256) void gn_bwd_fused_kernel(const dmd_gn_bwd_params p) {
   __shared__ float g_mean[GN_BWD_MAXG], g_rstd[GN_BWD_MAXG], g_m1[GN_BWD_MAXG], g_m2[GN_BWD_MAXG];
   __shared__ double red[4][GN_BWD_MAXG][2];
@@ -361,6 +363,107 @@ __global__ __launch_bounds__(256) void gn_bwd_fused_kernel(const dmd_gn_bwd_para
   __syncthreads();
   const float m1 = g_m1[g], m2 = g_m2[g];
   for (int pix = tid / CQ; pix < p.HW; pix += 256 / CQ) {
+    const size_t off = ((size_t)n * p.HW + pix) * C + c0;
+    if (!gn_bwd_exists(p, pix)) {
+      *(f32x4*)(p.dx + off) = (f32x4){0.f, 0.f, 0.f, 0.f};
+      continue;
+    }
+    const f32x4 xv = *(const f32x4*)(p.x + off);
+    const f32x4 dv = *(const f32x4*)(p.da + off);
+    f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (p.dskip) o = *(const f32x4*)(p.dskip + off);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const GnBwdElem r = gn_bwd_elem(xv[e], dv[e], mean, rstd, mul[e], add[e], p.identity_activation == 0);
+      o[e] += rstd * (r.dxh - m1 - r.xh * m2);
+    }
+    *(f32x4*)(p.dx + off) = o;
+  }
+}
+
+// gn_bwd_fused_kernel for every width the grouping rule allows up to 256 channels (dmd_gn_width_ok: the general groups of 48, 80,
+// 144 ... channels, where C / 4 need not divide 256), any HW, one workgroup per image: the threads behind the last whole row of
+// channel quads (256 - (256 / CQ) * CQ of them) take no pixel; everything else as there.
+__global__ __launch_bounds__(256) void gn_bwd_any_kernel(const dmd_gn_bwd_params p) {
+  __shared__ float g_mean[GN_BWD_MAXG], g_rstd[GN_BWD_MAXG], g_m1[GN_BWD_MAXG], g_m2[GN_BWD_MAXG];
+  __shared__ double red[4][GN_BWD_MAXG][2];
+  __shared__ float cred[256][8];
+  const int n = blockIdx.x, tid = threadIdx.x;
+  const int C = p.C, CQ = C / 4, G = C / DMD_GN_GROUP > 0 ? C / DMD_GN_GROUP : 1;
+  const int gsz = C / G;
+  const double cnt = (double)gsz * gn_bwd_count(p);
+  if (tid < G) {
+    float m, r;
+    dmd_finalize_stats(p.norm.stats + ((size_t)(n * G + tid) * p.norm.stat_tiles) * 2, p.norm.stat_tiles, cnt, &m, &r);
+    g_mean[tid] = m;
+    g_rstd[tid] = r;
+  }
+  __syncthreads();
+  const int q = tid % CQ;
+  const int c0 = 4 * q;
+  const int g = c0 / gsz;
+  const int pix_first = tid < (256 / CQ) * CQ ? tid / CQ : p.HW;
+  const float mean = g_mean[g], rstd = g_rstd[g];
+  float mul[4], add[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float m = p.norm.mul ? p.norm.mul[(size_t)n * p.norm.mul_stride + c0 + e] : 1.0f;
+    if (p.norm.mul_plus_one) m = 1.0f + m;
+    mul[e] = m;
+    add[e] = p.norm.add ? p.norm.add[(size_t)n * p.norm.add_stride + c0 + e] : 0.0f;
+  }
+  double s1 = 0.0, s2 = 0.0;
+  float dm[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int pix = pix_first; pix < p.HW; pix += 256 / CQ) {
+    if (!gn_bwd_exists(p, pix)) continue;
+    const size_t off = ((size_t)n * p.HW + pix) * C + c0;
+    const f32x4 xv = *(const f32x4*)(p.x + off);
+    const f32x4 dv = *(const f32x4*)(p.da + off);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const GnBwdElem r = gn_bwd_elem(xv[e], dv[e], mean, rstd, mul[e], add[e], p.identity_activation == 0);
+      s1 += (double)r.dxh;
+      s2 += (double)r.dxh * (double)r.xh;
+      dm[e] += r.du * r.xh;
+      db[e] += r.du;
+    }
+  }
+  for (int gg = 0; gg < G; ++gg) {
+    const double a = dmd_wave_sum(g == gg ? s1 : 0.0);
+    const double b = dmd_wave_sum(g == gg ? s2 : 0.0);
+    if ((tid & 63) == 0) {
+      red[tid >> 6][gg][0] = a;
+      red[tid >> 6][gg][1] = b;
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    cred[tid][e] = dm[e];
+    cred[tid][4 + e] = db[e];
+  }
+  __syncthreads();
+  if (tid < G) {
+    double a = 0.0, b = 0.0;
+    for (int w = 0; w < 4; ++w) {
+      a += red[w][tid][0];
+      b += red[w][tid][1];
+    }
+    g_m1[tid] = (float)(a / cnt);
+    g_m2[tid] = (float)(b / cnt);
+  }
+  if (tid < C) {
+    const int qq = tid >> 2, e = tid & 3;
+    float a = 0.f, b = 0.f;
+    for (int l = 0; l < 256 / CQ; ++l) {
+      a += cred[l * CQ + qq][e];
+      b += cred[l * CQ + qq][4 + e];
+    }
+    p.dmul[(size_t)n * C + tid] = a;
+    p.dadd[(size_t)n * C + tid] = b;
+  }
+  __syncthreads();
+  const float m1 = g_m1[g], m2 = g_m2[g];
+  for (int pix = pix_first; pix < p.HW; pix += 256 / CQ) {
     const size_t off = ((size_t)n * p.HW + pix) * C + c0;
     if (!gn_bwd_exists(p, pix)) {
       *(f32x4*)(p.dx + off) = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -544,9 +647,15 @@ extern "C" int dmd_gn_silu_bwd(const dmd_gn_bwd_params* pp, dmd_stream_t stream)
   DMD_CHECK_ARG((pp->W == 0 && pp->valid_h == 0 && pp->valid_w == 0) ||
                 (pp->W > 0 && pp->HW % pp->W == 0 && pp->valid_h > 0 && pp->valid_h <= pp->HW / pp->W && pp->valid_w > 0 && pp->valid_w <= pp->W),
                 "gn_silu_bwd: valid extent %d x %d of a (%d / %d) x %d tensor", pp->valid_h, pp->valid_w, pp->HW, pp->W, pp->W);
-  DMD_CHECK_ARG(pp->C % 4 == 0 && pp->C <= 256 && 256 % (pp->C / 4) == 0 && (pp->C % DMD_GN_GROUP == 0 || pp->C < DMD_GN_GROUP),
+  DMD_CHECK_ARG((pp->C <= 256 && dmd_gn_width_ok(pp->C)) || (pp->C % 4 == 0 && pp->C < DMD_GN_GROUP && 256 % (pp->C / 4) == 0),
                 "gn_silu_bwd: unsupported C %d", pp->C);
   dmd_gn_bwd_params p = *pp;
+  if (256 % (p.C / 4) != 0 || (p.C % DMD_GN_GROUP != 0 && p.C > DMD_GN_GROUP)) {
+    // the general groups (48, 80, 144 channels ...): one launch, a workgroup per image
+    hipLaunchKernelGGL(gn_bwd_any_kernel, dim3(p.N), dim3(256), 0, (hipStream_t)stream, p);
+    DMD_LAUNCH_CHECK();
+    return 0;
+  }
   const int T = gn_bwd_tiles(p.HW);
   const int G = p.C / DMD_GN_GROUP > 0 ? p.C / DMD_GN_GROUP : 1;
   double* group_partial = (double*)p.workspace;
@@ -605,7 +714,34 @@ struct WgradGeom {
   static constexpr int DY_FLOATS = 128 * SA;
   static constexpr int TAB_FLOATS = 2 * 3 * CIN;
   static constexpr int SMEM_BYTES = (PATCH_FLOATS + DY_FLOATS + TAB_FLOATS) * 4;
+  static constexpr bool GENG = false;  // a normalised source in groups of min(C, 32) channels
 };
+
+// general-group instances (GENG): the real channels [0, cin_real) of a normalised source form dmd_gn_group_size(cin_real)-channel
+// groups (dmd_common.h), the channels behind them are zero padding.  The host (ac_native._wgrad_tiled) launches them on one
+// whole group of 16, 48, 40, 36 ... channels zero-padded to the 64 -> 64 shape.
+template <int NCO_, int NCI_, int TAPS_>
+struct WgradGeomGN : WgradGeom<NCO_, NCI_, TAPS_> {
+  static constexpr bool GENG = true;
+};
+
+// the prologue's (mean, scale, shift) of channel c of image n
+template <class G>
+__device__ __forceinline__ void wgrad_norm_entry(const dmd_wgrad_params& p, int n, int c, int Cx, int Hv, int Wv, float* m, float* a,
+                                                 float* ad) {
+  if (G::GENG) {
+    const int gs = dmd_gn_group_size(p.cin_real);
+    if (c < p.cin_real) {
+      norm_entry_gs(p.src.norm, n, c, p.cin_real, gs, (double)gs * Hv * Wv, m, a, ad);
+    } else {
+      *m = 0.f;
+      *a = 0.f;
+      *ad = 0.f;
+    }
+  } else {
+    norm_entry(p.src.norm, n, c, Cx, (double)(Cx < DMD_GN_GROUP ? Cx : DMD_GN_GROUP) * Hv * Wv, m, a, ad);
+  }
+}
 
 struct SubTile {
   int n, y0, x0;
@@ -768,7 +904,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const dmd_wgrad_params p, in
         for (int c = tid; c < 2 * G::CIN; c += 256) {
           const int s = c / G::CIN, cc = c - s * G::CIN;
           float m, a, ad;
-          norm_entry(p.src.norm, s ? st[1].n : st[0].n, cc, Cx, (double)(Cx < DMD_GN_GROUP ? Cx : DMD_GN_GROUP) * Hv * Wv, &m, &a, &ad);
+          wgrad_norm_entry<G>(p, s ? st[1].n : st[0].n, cc, Cx, Hv, Wv, &m, &a, &ad);
           tab[(s * 3 + 0) * G::CIN + cc] = m;
           tab[(s * 3 + 1) * G::CIN + cc] = a;
           tab[(s * 3 + 2) * G::CIN + cc] = ad;
@@ -826,8 +962,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const dmd_wgrad_params p, in
       for (int c = tid; c < 2 * G::CIN; c += 256) {
         const int s = c / G::CIN, cc = c - s * G::CIN;
         float m, a, ad;
-        norm_entry(p.src.norm, s ? st[1].n : st[0].n, cc, Cx,  // (select, not st[s]: a per-lane index would put st[] in scratch)
-                   (double)(Cx < DMD_GN_GROUP ? Cx : DMD_GN_GROUP) * Hv * Wv, &m, &a, &ad);
+        // (select, not st[s]: a per-lane index would put st[] in scratch)
+        wgrad_norm_entry<G>(p, s ? st[1].n : st[0].n, cc, Cx, Hv, Wv, &m, &a, &ad);
         tab[(s * 3 + 0) * G::CIN + cc] = m;
         tab[(s * 3 + 1) * G::CIN + cc] = a;
         tab[(s * 3 + 2) * G::CIN + cc] = ad;
@@ -1080,7 +1216,7 @@ __global__ __launch_bounds__(512) void wgrad_ps_kernel(const dmd_wgrad_params p,
     auto build_table = [&](int img, int which) __attribute__((always_inline)) {
       if (ptid < G::CIN) {
         float m, a, ad;
-        norm_entry(p.src.norm, img, ptid, Cx, (double)(Cx < DMD_GN_GROUP ? Cx : DMD_GN_GROUP) * Hv * Wv, &m, &a, &ad);
+        wgrad_norm_entry<G>(p, img, ptid, Cx, Hv, Wv, &m, &a, &ad);
         float* t = tab + which * 3 * G::CIN;
         t[ptid] = m;
         t[G::CIN + ptid] = a;
@@ -1373,9 +1509,9 @@ extern "C" int64_t dmd_wgrad_workspace_floats(const dmd_wgrad_params* p) {
   return (int64_t)(max_wg + WGRAD_SLICES) * (NB * NCO * 256 + p->Cout);
 }
 
-template <int NCO, int NCI, int TAPS>
-static int launch_wgrad(const dmd_wgrad_params& p, hipStream_t st) {
-  using G = WgradGeom<NCO, NCI, TAPS>;
+template <class G>
+static int launch_wgrad_g(const dmd_wgrad_params& p, hipStream_t st) {
+  constexpr int NCO = G::NCO, NCI = G::NCI, TAPS = G::TAPS;
   int tiles, num_wg, tpw;
   wgrad_plan(&p, &tiles, &num_wg, &tpw);
   static bool attr_set[DMD_MAX_DEVICES] = {};  // per instantiation AND per device
@@ -1386,8 +1522,8 @@ static int launch_wgrad(const dmd_wgrad_params& p, hipStream_t st) {
                                        G::SMEM_BYTES);
     if (e == hipSuccess)
       e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<G, true>), hipFuncAttributeMaxDynamicSharedMemorySize, G::SMEM_BYTES);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_ps_kernel<G, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (e == hipSuccess && !G::GENG)  // (a general-group launch always has a prologue)
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_ps_kernel<G, G::GENG>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               WgradPs<G>::SMEM_BYTES);
     if (e == hipSuccess)
       e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_ps_kernel<G, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1398,10 +1534,10 @@ static int launch_wgrad(const dmd_wgrad_params& p, hipStream_t st) {
   // DIAMOND_WGRAD_PS=0: the split-fp16 gradient on the single-role kernel (A/B, and the tests' bitwise comparison of the two)
   static DmdEnvInt ps_env{"DIAMOND_WGRAD_PS", 1};
   if ((p.precision & 0xff) == DMD_PRECISION_F16X2 && ps_env.get() != 0) {
-    if (p.src.prologue != DMD_PROLOGUE_NONE)
+    if (G::GENG || p.src.prologue != DMD_PROLOGUE_NONE)
       hipLaunchKernelGGL((wgrad_ps_kernel<G, true>), dim3(num_wg), dim3(512), WgradPs<G>::SMEM_BYTES, st, p, tiles, tpw);
     else
-      hipLaunchKernelGGL((wgrad_ps_kernel<G, false>), dim3(num_wg), dim3(512), WgradPs<G>::SMEM_BYTES, st, p, tiles, tpw);
+      hipLaunchKernelGGL((wgrad_ps_kernel<G, G::GENG>), dim3(num_wg), dim3(512), WgradPs<G>::SMEM_BYTES, st, p, tiles, tpw);
   } else if ((p.precision & 0xff) == DMD_PRECISION_F16X2)
     hipLaunchKernelGGL((wgrad_kernel<G, true>), dim3(num_wg), dim3(256), G::SMEM_BYTES, st, p, tiles, tpw);
   else
@@ -1422,6 +1558,17 @@ static int launch_wgrad(const dmd_wgrad_params& p, hipStream_t st) {
   hipLaunchKernelGGL(wgrad_reduce2_kernel, dim3((per_total + 255) / 256), dim3(256), 0, st, (const float*)ws2, WGRAD_SLICES, G::NB,
                      NCO, NCI, TAPS, p.cin_real, p.dw, p.dbias);
   return 0;
+}
+
+// a normalised source whose groups are not min(C, 32) channels of src.C: dmd_gn_group_size(cin_real) (see WgradGeomGN)
+static bool wgrad_geng(const dmd_wgrad_params& p) {
+  const int Cx = p.src.C;
+  return p.src.prologue != DMD_PROLOGUE_NONE && dmd_gn_group_size(p.cin_real) != (Cx < DMD_GN_GROUP ? Cx : DMD_GN_GROUP);
+}
+
+template <int NCO, int NCI, int TAPS>
+static int launch_wgrad(const dmd_wgrad_params& p, hipStream_t st) {
+  return launch_wgrad_g<WgradGeom<NCO, NCI, TAPS>>(p, st);
 }
 
 extern "C" int dmd_wgrad_job(const dmd_wgrad_params* p, dmd_wgrad_reduce_job* job) {
@@ -1483,7 +1630,12 @@ extern "C" int dmd_conv2d_wgrad(const dmd_wgrad_params* p, dmd_stream_t stream) 
   const int nco = p->Cout / 16, nci = p->src.C / 16;
   DMD_CHECK_ARG(p->Cout % 16 == 0 && p->src.C % 16 == 0, "wgrad: channels must be multiples of 16");
   int rc = -1;
-  if (p->taps == 9) {
+  if (wgrad_geng(*p)) {
+    DMD_CHECK_ARG(nco == 4 && nci == 4 && p->cin_real % 4 == 0 && p->cin_real <= 64,
+                  "wgrad: a normalised source in groups of %d channels needs the 64 -> 64 shape and a whole group (cin_real %d of %d)",
+                  dmd_gn_group_size(p->cin_real), p->cin_real, p->src.C);
+    rc = p->taps == 9 ? launch_wgrad_g<WgradGeomGN<4, 4, 9>>(*p, st) : launch_wgrad_g<WgradGeomGN<4, 4, 1>>(*p, st);
+  } else if (p->taps == 9) {
     if (nco == 2 && nci == 1) rc = launch_wgrad<2, 1, 9>(*p, st);
     else if (nco == 4 && nci == 1) rc = launch_wgrad<4, 1, 9>(*p, st);  // denoiser conv_in (15 -> 64)
     else if (nco == 1 && nci == 4) rc = launch_wgrad<1, 4, 9>(*p, st);  // denoiser conv_out (64 -> 3, dy padded to 16)

@@ -88,7 +88,33 @@ __device__ __forceinline__ double dmd_wave_sum(double v) {
   return v;
 }
 
-// per-channel affine of a GroupNorm(+FiLM): y = (x - mean) * a + add
+// The grouping rule (models/blocks.py:27,38): C channels form G = max(1, C / 32) groups of C / G channels -- 32 whenever C is a
+// multiple of 32, else e.g. 16 (C = 16), 48 (48), 40 (80), 36 (144).  The kernels instantiated for the default configuration
+// assume groups of 32 (or one group of C < 32); the "general group" (GENG) instances follow this rule.
+__host__ __device__ __forceinline__ int dmd_gn_groups(int C) { return C / DMD_GN_GROUP > 0 ? C / DMD_GN_GROUP : 1; }
+__host__ __device__ __forceinline__ int dmd_gn_group_size(int C) { return C / dmd_gn_groups(C); }
+// a normalised width the general-group kernels take: the reference's groups divide C, a channel quad never straddles two of
+// them, C a multiple of the kernels' 16-channel granularity, and at most 256 channels unless the groups are the 32 of the
+// default instances
+__host__ __device__ __forceinline__ bool dmd_gn_width_ok(int C) {
+  return C > 0 && C % 16 == 0 && C % dmd_gn_groups(C) == 0 && dmd_gn_group_size(C) % 4 == 0 && (C % DMD_GN_GROUP == 0 || C <= 256);
+}
+
+// per-channel affine of a GroupNorm(+FiLM) in groups of gs channels: y = (x - mean) * a + add
+__device__ __forceinline__ void norm_entry_gs(const dmd_norm& nm, int n, int c, int C, int gs, double count, float* mean,
+                                              float* a, float* add) {
+  const int G = C / gs;
+  const int g = c / gs;
+  float m, rstd;
+  dmd_finalize_stats(nm.stats + ((size_t)(n * G + g) * nm.stat_tiles) * 2, nm.stat_tiles, count, &m, &rstd);
+  float mul = nm.mul ? nm.mul[(size_t)n * nm.mul_stride + c] : 1.0f;
+  if (nm.mul_plus_one) mul = 1.0f + mul;
+  *mean = m;
+  *a = rstd * mul;
+  *add = nm.add ? nm.add[(size_t)n * nm.add_stride + c] : 0.0f;
+}
+
+// per-channel affine of a GroupNorm(+FiLM) in groups of 32 (one group when C < 32): y = (x - mean) * a + add
 __device__ __forceinline__ void norm_entry(const dmd_norm& nm, int n, int c, int C, double count, float* mean,
                                            float* a, float* add) {
   const int G = C / DMD_GN_GROUP > 0 ? C / DMD_GN_GROUP : 1;

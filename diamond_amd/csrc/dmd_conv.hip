@@ -56,7 +56,26 @@ struct ConvGeom {
   // minimum waves per SIMD the kernel is compiled for: the 64-cout 3x3 stride-1 instance on 8x8 patches (8 m-blocks per
   // wave + nine prefetched weight fragments) does not fit 256 registers -- one workgroup per SIMD set instead of spilling
   static constexpr int MIN_WAVES = (WN_ == 4 && CFGB_ && TAPS_ == 9 && STRIDE_ == 1) ? 1 : 2;
+  static constexpr bool GENG = false;  // normalised sources / residual in groups of 32 (one group when C < 32)
 };
+
+// the general-group instances (GENG): a normalised source or residual of C channels is normalised in groups of
+// dmd_gn_group_size(C) (16, 48, 40, 36 ... channels: dmd_common.h).  Selected by the host only where such a width is
+// normalised; everything else -- the default configuration -- keeps the ConvGeom instances.
+template <int WN_, bool CFGB_, int TAPS_, int STRIDE_, bool SPLIT_ = false>
+struct ConvGeomGN : ConvGeom<WN_, CFGB_, TAPS_, STRIDE_, SPLIT_> {
+  static constexpr bool GENG = true;
+};
+
+template <class G>
+__device__ __forceinline__ void conv_norm_entry(const dmd_norm& nm, int n, int c, int C, int hv, int wv, float* m, float* a, float* ad) {
+  if (G::GENG) {
+    const int gs = dmd_gn_group_size(C);
+    norm_entry_gs(nm, n, c, C, gs, (double)gs * hv * wv, m, a, ad);
+  } else {
+    norm_entry(nm, n, c, C, (double)DMD_GN_GROUP * hv * wv, m, a, ad);
+  }
+}
 
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
@@ -144,7 +163,7 @@ __global__ __launch_bounds__(256, G::MIN_WAVES) void conv_mfma_kernel(const dmd_
     for (int s = 0; s < G::SUB; ++s) {
       float m = 0.f, a = 1.f, ad = 0.f;
       if (sc.prologue != DMD_PROLOGUE_NONE && ti[s].valid)
-        norm_entry(sc.norm, ti[s].n, cl, sc.C, (double)DMD_GN_GROUP * Hvs * Wvs, &m, &a, &ad);
+        conv_norm_entry<G>(sc.norm, ti[s].n, cl, sc.C, Hvs, Wvs, &m, &a, &ad);
       tab_mean[s][c] = m;
       tab_a[s][c] = a;
       tab_add[s][c] = ad;
@@ -157,7 +176,7 @@ __global__ __launch_bounds__(256, G::MIN_WAVES) void conv_mfma_kernel(const dmd_
         float m = 0.f, a = 1.f, ad = 0.f;
         const int cc = cout_group0 + c;
         if (ti[s].valid && cc < p.Cout)
-          norm_entry(p.residual_norm, ti[s].n, cc, p.Cout, (double)DMD_GN_GROUP * Hvo * Wvo, &m, &a, &ad);
+          conv_norm_entry<G>(p.residual_norm, ti[s].n, cc, p.Cout, Hvo, Wvo, &m, &a, &ad);
         rtab[s][0][c] = m;
         rtab[s][1][c] = a;
         rtab[s][2][c] = ad;
@@ -528,7 +547,8 @@ static int validate_conv(const dmd_conv_params* p) {
     DMD_CHECK_ARG(p->src[i].x && p->src[i].C > 0 && p->src[i].C % 16 == 0, "conv: src %d channels %d", i, p->src[i].C);
     if (p->src[i].prologue != DMD_PROLOGUE_NONE) {
       DMD_CHECK_ARG(p->src[i].norm.stats && p->src[i].norm.stat_tiles > 0, "conv: src %d prologue without stats", i);
-      DMD_CHECK_ARG(p->src[i].C % DMD_GN_GROUP == 0, "conv: normalised source needs C %% 32 == 0");
+      DMD_CHECK_ARG(dmd_gn_width_ok(p->src[i].C), "conv: normalised source of %d channels (C %% 32 == 0, or C <= 256 in groups of "
+                    "C / max(1, C / 32) channels, a multiple of 4)", p->src[i].C);
     }
     cin += p->src[i].C;
   }
@@ -536,7 +556,7 @@ static int validate_conv(const dmd_conv_params* p) {
   DMD_CHECK_ARG(p->Cout > 0 && p->CoutPad >= p->Cout && p->CoutPad % 16 == 0, "conv: Cout/CoutPad");
   DMD_CHECK_ARG(p->w && p->out, "conv: null weight/out");
   if (p->out_stats) DMD_CHECK_ARG(p->Cout % DMD_GN_GROUP == 0 && p->CoutPad == p->Cout, "conv: out_stats needs Cout %% 32 == 0");
-  if (p->residual_norm.stats) DMD_CHECK_ARG(p->residual && p->Cout % DMD_GN_GROUP == 0, "conv: residual_norm");
+  if (p->residual_norm.stats) DMD_CHECK_ARG(p->residual && dmd_gn_width_ok(p->Cout), "conv: residual_norm");
   if (p->upsample) DMD_CHECK_ARG(p->H % 2 == 0 && p->W % 2 == 0, "conv: upsample needs even output");
   DMD_CHECK_ARG(p->valid_h >= 0 && p->valid_h <= p->H && p->valid_w >= 0 && p->valid_w <= p->W && (p->valid_h == 0) == (p->valid_w == 0),
                 "conv: valid extent %d x %d outside the %d x %d buffer", p->valid_h, p->valid_w, p->H, p->W);
@@ -545,6 +565,13 @@ static int validate_conv(const dmd_conv_params* p) {
     DMD_CHECK_ARG(dmd_conv2d_proj_eligible(p), "conv: fused skip projection on parameters dmd_conv2d_proj_eligible() rejects "
                   "(needs F16X2 3x3 stride 1, Cout 64, H, W %% 16 == 0, two 64-channel sources, no residual)");
   return 0;
+}
+
+// a normalised source or residual whose groups are not the default instances' 32 channels
+static bool conv_geng(const dmd_conv_params& p) {
+  for (int i = 0; i < p.nsrc; ++i)
+    if (p.src[i].prologue != DMD_PROLOGUE_NONE && p.src[i].C % DMD_GN_GROUP != 0) return true;
+  return p.residual_norm.stats && p.Cout % DMD_GN_GROUP != 0;
 }
 
 // an "f16x2" launch that conv_f16ws does not cover (stride 2, qkv / out_proj, odd shapes, the data gradients of the training
@@ -556,7 +583,12 @@ static void launch_conv(const dmd_conv_params& p, int groups, hipStream_t st) {
   using G = ConvGeom<WN, CFGB, TAPS, STRIDE>;
   const int tiles = (p.H / G::TH) * (p.W / G::TW) * p.N;
   dim3 grid((tiles + G::SUB - 1) / G::SUB, groups);
-  if (conv_mfma_split(p))
+  if (conv_geng(p)) {
+    if (conv_mfma_split(p))
+      hipLaunchKernelGGL((conv_mfma_kernel<ConvGeomGN<WN, CFGB, TAPS, STRIDE, true>>), grid, dim3(256), 0, st, p);
+    else
+      hipLaunchKernelGGL((conv_mfma_kernel<ConvGeomGN<WN, CFGB, TAPS, STRIDE>>), grid, dim3(256), 0, st, p);
+  } else if (conv_mfma_split(p))
     hipLaunchKernelGGL((conv_mfma_kernel<ConvGeom<WN, CFGB, TAPS, STRIDE, true>>), grid, dim3(256), 0, st, p);
   else
     hipLaunchKernelGGL((conv_mfma_kernel<G>), grid, dim3(256), 0, st, p);
@@ -615,7 +647,7 @@ extern "C" int dmd_conv2d_kernel_name(const dmd_conv_params* p, char* buf, int b
     snprintf(buf, buf_len, "conv_f16ws_kernel<WsGeom<%s, %d, %d>>", b8 ? "true" : "false", p->CoutPad == 64 ? 2 : 1, p->taps);
   } else {
     const int wn = p->CoutPad % 64 == 0 ? 4 : (p->CoutPad % 32 == 0 ? 2 : 1);
-    snprintf(buf, buf_len, "conv_mfma_kernel<ConvGeom<%d, %s, %d, %d, %s>>", wn, b8 ? "true" : "false", p->taps, p->stride,
+    snprintf(buf, buf_len, "conv_mfma_kernel<%s<%d, %s, %d, %d, %s>>", conv_geng(*p) ? "ConvGeomGN" : "ConvGeom", wn, b8 ? "true" : "false", p->taps, p->stride,
              conv_mfma_split(*p) ? "true" : "false");
   }
   return 0;
@@ -624,6 +656,7 @@ extern "C" int dmd_conv2d_kernel_name(const dmd_conv_params* p, char* buf, int b
 extern "C" int dmd_conv2d_naive(const dmd_conv_params* p, dmd_stream_t stream) {
   if (int e = validate_conv(p)) return e;
   DMD_CHECK_ARG(!p->proj_nsrc, "naive conv: no fused skip projection (run the projection as its own launch)");
+  DMD_CHECK_ARG(!conv_geng(*p), "naive conv: normalisation in groups of 32 channels only");
   hipStream_t st = (hipStream_t)stream;
   const size_t total = (size_t)p->N * p->H * p->W * p->Cout;
   dmd_conv_params q = *p;

@@ -1310,6 +1310,9 @@ extern "C" int dmd_conv2d_f16x2_eligible(const dmd_conv_params* p) {
   if (!p || (p->precision & 0xff) != DMD_PRECISION_F16X2 || !p->w_f16) return 0;
   if (p->stride != 1 || p->residual_norm.stats || (p->taps != 9 && p->taps != 1)) return 0;
   if (p->taps == 1 && p->upsample) return 0;
+  // normalised sources in groups of 32 only (other widths: the general-group instances of the generic kernel)
+  for (int i = 0; i < p->nsrc; ++i)
+    if (p->src[i].prologue != DMD_PROLOGUE_NONE && p->src[i].C % DMD_GN_GROUP != 0) return 0;
   // few-channel NCHW head (conv_out): Cout <= 4 zero-padded to 32, no residual / statistics
   const bool head = p->out_nchw && p->Cout <= 4 && p->CoutPad == 32 && !p->residual && !p->out_stats;
   if (!head && ((p->Cout != 64 && p->Cout != 32) || p->CoutPad != p->Cout || p->out_nchw)) return 0;

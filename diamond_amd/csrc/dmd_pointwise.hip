@@ -221,6 +221,47 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
   }
 }
 
+// ---- the same statistics for groups of any size the grouping rule gives (dmd_gn_group_size: 16, 48, 40, 36 ... channels, a
+// multiple of 4): grid (G, N), 256 threads, thread -> (pixel, channel quad of the group) in a flat walk; same layout, fp64 sums
+__global__ __launch_bounds__(256) void gn_stats_any_kernel(const float* __restrict__ x, double* __restrict__ stats, int HW, int C, int W,
+                                                           int hv, int wv) {
+  __shared__ double red[4][2];
+  const int g = blockIdx.x, n = blockIdx.y, G = gridDim.x;
+  const int tid = threadIdx.x;
+  const int gq = C / G / 4;  // channel quads per group
+  double s = 0.0, ss = 0.0;
+  for (int i = tid; i < HW * gq; i += 256) {
+    const int pix = i / gq, quad = i - pix * gq;
+    if (W > 0) {
+      const int py = pix / W;
+      if (py >= hv || pix - py * W >= wv) continue;
+    }
+    const f32x4 v = *(const f32x4*)(x + ((size_t)n * HW + pix) * C + g * gq * 4 + quad * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const double d = (double)v[e];
+      s += d;
+      ss += d * d;
+    }
+  }
+  s = dmd_wave_sum(s);
+  ss = dmd_wave_sum(ss);
+  if ((tid & 63) == 0) {
+    red[tid >> 6][0] = s;
+    red[tid >> 6][1] = ss;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double a = 0.0, b = 0.0;
+    for (int w = 0; w < 4; ++w) {
+      a += red[w][0];
+      b += red[w][1];
+    }
+    stats[((size_t)n * G + g) * 2] = a;
+    stats[((size_t)n * G + g) * 2 + 1] = b;
+  }
+}
+
 // ---- 2x2 max pool, NHWC; one thread per (output pixel, channel quad) ---------------------------
 // argmax: index 0..3 (dy*2+dx) of the FIRST maximum in scan order (ATen max_pool2d picks the
 // first max it meets scanning h then w; ties only matter for the backward routing).
@@ -666,17 +707,25 @@ extern "C" int dmd_nhwc_to_nchw(const float* in, float* out, int N, int C, int H
   return 0;
 }
 
+// groups of 32: gn_stats_kernel; any other width the grouping rule allows (dmd_gn_width_ok): gn_stats_any_kernel
 extern "C" int dmd_gn_stats(const float* x, double* stats, int N, int HW, int C, dmd_stream_t stream) {
-  DMD_CHECK_ARG(x && stats && C % DMD_GN_GROUP == 0, "gn_stats: C %% 32");
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(C / DMD_GN_GROUP, N), dim3(256), 0, (hipStream_t)stream, x, stats, HW, C, 0, 0, 0);
+  DMD_CHECK_ARG(x && stats && dmd_gn_width_ok(C), "gn_stats: C %d (needs C %% 32 == 0, or C <= 256, C %% 16 == 0 and groups of a multiple of 4)", C);
+  if (C % DMD_GN_GROUP == 0)
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(C / DMD_GN_GROUP, N), dim3(256), 0, (hipStream_t)stream, x, stats, HW, C, 0, 0, 0);
+  else
+    hipLaunchKernelGGL(gn_stats_any_kernel, dim3(dmd_gn_groups(C), N), dim3(256), 0, (hipStream_t)stream, x, stats, HW, C, 0, 0, 0);
   DMD_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dmd_gn_stats_valid(const float* x, double* stats, int N, int H, int W, int valid_h, int valid_w, int C, dmd_stream_t stream) {
-  DMD_CHECK_ARG(x && stats && C % DMD_GN_GROUP == 0, "gn_stats: C %% 32");
+  DMD_CHECK_ARG(x && stats && dmd_gn_width_ok(C), "gn_stats: C %d (needs C %% 32 == 0, or C <= 256, C %% 16 == 0 and groups of a multiple of 4)", C);
   DMD_CHECK_ARG(valid_h > 0 && valid_h <= H && valid_w > 0 && valid_w <= W, "gn_stats: valid extent %d x %d of %d x %d", valid_h, valid_w, H, W);
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(C / DMD_GN_GROUP, N), dim3(256), 0, (hipStream_t)stream, x, stats, H * W, C, W, valid_h, valid_w);
+  if (C % DMD_GN_GROUP == 0)
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(C / DMD_GN_GROUP, N), dim3(256), 0, (hipStream_t)stream, x, stats, H * W, C, W, valid_h, valid_w);
+  else
+    hipLaunchKernelGGL(gn_stats_any_kernel, dim3(dmd_gn_groups(C), N), dim3(256), 0, (hipStream_t)stream, x, stats, H * W, C, W, valid_h,
+                       valid_w);
   DMD_LAUNCH_CHECK();
   return 0;
 }

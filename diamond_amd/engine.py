@@ -51,6 +51,13 @@ class AttnRecord:
     head_dim: int
 
 
+@dataclass
+class CatRecord:
+    """A channel concatenation materialised by the forward (engine.concat): its gradient goes back to the sources by channels."""
+    srcs: list  # [Act]
+    out: "Act"
+
+
 # recording tape of the current forward (None: inference, nothing is recorded)
 TAPE: Optional[list] = None
 
@@ -526,15 +533,21 @@ def new_stats(n: int, c: int, tiles: int, device) -> Tensor:
 CONV_CIN_MAX = 256  # input channels (all sources together) of ONE dmd_conv2d launch: DMD_CIN_MAX, csrc/dmd_conv.hip
 
 
+def gn_group_size(c: int) -> int:
+    """Channels per GroupNorm group of a normalised width (the reference's rule, blocks.py:27,38: max(1, C // 32) groups)."""
+    return c // max(1, c // nv.GN_GROUP)
+
+
 def _channel_slice(a: Act, prologue: int, norm: Optional[NormSpec], c0: int, c1: int) -> Tuple[Act, int, Optional[NormSpec]]:
     """Channels [c0, c1) of a source as a source of its own: a contiguous copy of the slice, the partial GroupNorm sums of its
-    groups (whole 32-channel groups: the statistics of a group do not depend on the others) and the matching columns of its
+    groups (whole groups: the statistics of a group do not depend on the others) and the matching columns of its
     multiplicative / additive parameters (views: the kernels take pointer + row stride)."""
     sub = Act(a.t[..., c0:c1].contiguous(), None, 0, a.needs_grad, a.valid)
     if prologue == nv.PROLOGUE_NONE:
         return sub, prologue, None
-    g = nv.GN_GROUP
+    g = gn_group_size(a.C)
     assert c0 % g == 0 and c1 % g == 0 and a.stats is not None, f"normalised source of {a.C} channels cut at [{c0}, {c1}): not whole GroupNorm groups"
+    assert gn_group_size(c1 - c0) == g, f"a {c1 - c0}-channel slice of {a.C} channels would be normalised in other groups"
     sub.stats, sub.tiles = a.stats[:, c0 // g:c1 // g].contiguous(), a.tiles
     cut = lambda t: None if t is None else t[..., c0:]
     return sub, prologue, NormSpec(cut(norm.mul), cut(norm.add), norm.mul_stride, norm.add_stride, norm.plus_one)
@@ -672,7 +685,9 @@ def conv2d(
         p.proj_w_f16 = nv.ptr(p_w16)
         p.proj_bias = nv.ptr(p_bias)
     stats, tiles = None, 0
-    if want_stats:
+    # (an output normalised in groups other than 32 channels: its statistics by dmd_gn_stats after the launch, below)
+    fused_stats = want_stats and cout % nv.GN_GROUP == 0
+    if fused_stats:
         tiles = nv.conv_stat_tiles(h, w)
         stats = new_stats(n, cout, tiles, dev)
         p.out_stats = nv.ptr(stats)
@@ -687,6 +702,9 @@ def conv2d(
             nbytes += 4.0 * sum(a.t.numel() for a in proj[0])
         nv.PROFILER.annotate(kernel_key(p), flops, nbytes)
     nv.check(fn(C.byref(p), nv.stream()), "dmd_conv2d")
+    if want_stats and not fused_stats:
+        assert not out_nchw, "statistics of an NCHW result"
+        stats, tiles = gn_stats(out, valid).stats, 1
     result = Act(out, stats, tiles, valid=valid)
     if TAPE is not None:
         assert module is not None, "recording a conv launch that does not name its nn.Conv2d"
@@ -716,6 +734,28 @@ def proj_fusable(xs: Sequence[Act], cout: int, precision: str, naive: Optional[b
         return False
     return (cout == 64 and hh % 16 == 0 and ww % 16 == 0 and len(xs) == 2 and all(a.C == 64 for a in xs)
             and n * hh * ww * 256 < 2 ** 32)
+
+
+def straddles(xs: Sequence[Act]) -> bool:
+    """True when the GroupNorm groups of the channel concatenation of `xs` cut through a source (the reference normalises the
+    concatenation, blocks.py:174,141-143: e.g. cat(144, 80) in groups of 32, cat(48, 48) in groups of 32): the consumer
+    convolution normalises each source with its own statistics, so such a concatenation has to be materialised (concat)."""
+    if len(xs) < 2:
+        return False
+    g = gn_group_size(sum(a.C for a in xs))
+    return any(a.C % g != 0 for a in xs[:-1])
+
+
+def concat(xs: Sequence[Act]) -> Act:
+    """The channel concatenation of `xs` as ONE NHWC tensor (a copy: plain data movement) with its GroupNorm statistics over the
+    whole tensor.  Recorded for the training backward (CatRecord: the gradient is split back by channels).  Only for
+    concatenations whose groups straddle their sources (straddles): never at the default configuration."""
+    valid = {a.valid for a in xs}
+    assert len(valid) == 1, f"sources with different valid extents: {valid}"
+    out = gn_stats(torch.cat([a.t for a in xs], dim=-1), valid.pop())
+    if TAPE is not None:
+        TAPE.append(CatRecord(list(xs), out))
+    return out
 
 
 def gn_stats(t: Tensor, valid: Optional[Tuple[int, int]] = None) -> Act:

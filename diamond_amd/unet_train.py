@@ -30,7 +30,7 @@ from torch import Tensor, nn
 from . import engine as E
 from . import native as nv
 from .ac_native import WgradBatch, _gn_bwd_instance, _gn_silu_bwd, _transposed, _wgrad, gn_bwd_sliced
-from .engine import Act, AttnRecord, ConvRecord, NormSpec
+from .engine import Act, AttnRecord, CatRecord, ConvRecord, NormSpec
 
 TRAIN_PRECISION = "f16x2"  # arithmetic of the forward, dgrad and wgrad convolutions (split-fp16 operands, fp32 accumulate); "f32" = exact
 
@@ -187,6 +187,16 @@ def backward_tape(tape: List, cache: E.PackCache, d_out: Tensor, table: Tensor, 
             nv.check(nv.lib().dmd_attention_bwd(nv.fptr(rec.qkv.t), nv.fptr(rec.out), nv.fptr(dyc), nv.fptr(dqkv),
                                                 nv.fptr(ws), n, h * w, rec.c, rec.head_dim, nv.stream()), "dmd_attention_bwd")
             grads.add(rec.qkv.t, dqkv)
+            continue
+        if isinstance(rec, CatRecord):  # a materialised channel concatenation (engine.concat): the gradient split by channels
+            dy = grads.pop(rec.out.t)
+            if dy is None:
+                continue
+            c0 = 0
+            for a in rec.srcs:
+                if a.needs_grad:
+                    grads.add(a.t, dy[..., c0:c0 + a.C].contiguous())
+                c0 += a.C
             continue
         dout = grads.pop(rec.out.t)
         if dout is None:

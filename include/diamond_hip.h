@@ -26,8 +26,14 @@ typedef void* dmd_stream_t; /* hipStream_t */
 #define DMD_GN_GROUP 32 /* models/blocks.py:12 GN_GROUP_SIZE */
 
 /* GroupNorm statistics travel between kernels as per-tile partial sums in fp64:
- * stats[((n * G + g) * T + t) * 2 + {0: sum x, 1: sum x^2}], G = C / 32, T = producer tiles
- * per image.  The consumer reduces the T partials in a fixed order (deterministic). */
+ * stats[((n * G + g) * T + t) * 2 + {0: sum x, 1: sum x^2}], T = producer tiles per image.
+ * The consumer reduces the T partials in a fixed order (deterministic).
+ * Grouping rule (models/blocks.py:27,38): C channels form G = max(1, C / 32) groups of C / G channels -- 32 whenever
+ * C % 32 == 0, else e.g. 16, 48, 40, 36 channels at C = 16, 48, 80, 144.  A normalised width must be C % 32 == 0, or
+ * C <= 256 with C % 16 == 0, C % G == 0 and C / G a multiple of 4.  dmd_conv2d emits out_stats for Cout % 32 == 0 only
+ * (other widths: dmd_gn_stats on its output).  dmd_conv2d_wgrad normalises the real channels [0, cin_real) of its source in
+ * groups of that rule applied to cin_real where those differ from min(C, 32) channels of src.C (then: one whole group,
+ * zero-padded to Cout = C = 64). */
 typedef struct dmd_norm {
   const double* stats;   /* NULL <=> no normalisation                                  */
   int32_t stat_tiles;    /* T                                                          */
