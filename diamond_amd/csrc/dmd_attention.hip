@@ -482,3 +482,138 @@ extern "C" int dmd_attention_bwd(const float* qkv, const float* y, const float* 
   DMD_LAUNCH_CHECK();
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// dmd_attention_bwd_valid -- the gradient of dmd_attention_valid: the same two kernels over the (vh, vw) part of an (H, W) token
+// grid (dmd_conv_params: VALID EXTENT).  Thread li <-> valid token (li / vw, li % vw); the sweeps walk the valid rows and columns
+// in token order, so with (vh, vw) == (H, W) every sum is formed as in dmd_attention_bwd (bitwise the same result).  Nothing
+// outside the extent is read (the margins of qkv / y / dy are unspecified, NaN included); the rows kernel's workgroups behind the
+// valid ones write the dqkv rows outside the extent as zero.  rowstat is indexed by the valid token.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void attention_bwd_valid_rows_kernel(const float* __restrict__ qkv, const float* __restrict__ y,
+                                                                      const float* __restrict__ dy, float* __restrict__ dqkv,
+                                                                      float* __restrict__ rowstat, int T, int W, int vh, int vw,
+                                                                      int C, int nbv) {
+  const int h = blockIdx.y, n = blockIdx.z, NH = C / 8, V = vh * vw;
+  if ((int)blockIdx.x >= nbv) {
+    // the m-th token outside the extent: rows < vh, columns >= vw first, then the rows >= vh
+    const int m = ((int)blockIdx.x - nbv) * 64 + threadIdx.x, side = vh * (W - vw);
+    if (m >= T - V) return;
+    int r, c;
+    if (m < side) {
+      r = m / (W - vw);
+      c = vw + (m - r * (W - vw));
+    } else {
+      r = vh + (m - side) / W;
+      c = (m - side) - (r - vh) * W;
+    }
+    float* o = dqkv + ((size_t)n * T + (size_t)r * W + c) * 3 * C + h * 8;
+    const f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      *(f32x4*)(o + t * C) = z;
+      *(f32x4*)(o + t * C + 4) = z;
+    }
+    return;
+  }
+  const int li = blockIdx.x * 64 + threadIdx.x;
+  if (li >= V) return;
+  const int qr = li / vw, i = qr * W + (li - qr * vw);
+  const float scale = 0.35355339059327373f;  // 1 / sqrt(8)
+  const size_t row = ((size_t)n * T + i);
+  const f8 q = ld8(qkv + row * 3 * C + h * 8);
+  const f8 yo = ld8(y + row * C + h * 8), dyo = ld8(dy + row * C + h * 8);
+  const float D = dot8(dyo, yo);
+  const float* kbase = qkv + (size_t)n * T * 3 * C + C + h * 8;
+  const float* vbase = kbase + C;
+  float m = -INFINITY, l = 0.f;
+  for (int jr = 0; jr < vh; ++jr) {
+    const float* krow = kbase + (size_t)jr * W * 3 * C;
+    for (int jc = 0; jc < vw; ++jc) {
+      const float s = dot8(q, ld8(krow + (size_t)jc * 3 * C)) * scale;
+      const float mn = fmaxf(m, s);
+      l = l * expf(m - mn) + expf(s - mn);
+      m = mn;
+    }
+  }
+  f8 dq;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) dq.v[e] = 0.f;
+  for (int jr = 0; jr < vh; ++jr) {
+    const float* krow = kbase + (size_t)jr * W * 3 * C;
+    const float* vrow = vbase + (size_t)jr * W * 3 * C;
+    for (int jc = 0; jc < vw; ++jc) {
+      const f8 k = ld8(krow + (size_t)jc * 3 * C);
+      const float s = dot8(q, k) * scale;
+      const float p = expf(s - m) / l;
+      const float ds = p * (dot8(dyo, ld8(vrow + (size_t)jc * 3 * C)) - D);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) dq.v[e] = __builtin_fmaf(ds * scale, k.v[e], dq.v[e]);
+    }
+  }
+  float* o = dqkv + row * 3 * C + h * 8;
+  *(f32x4*)o = (f32x4){dq.v[0], dq.v[1], dq.v[2], dq.v[3]};
+  *(f32x4*)(o + 4) = (f32x4){dq.v[4], dq.v[5], dq.v[6], dq.v[7]};
+  float* rs = rowstat + (((size_t)n * NH + h) * V + li) * 4;
+  rs[0] = m;
+  rs[1] = l;
+  rs[2] = D;
+}
+
+__global__ __launch_bounds__(64) void attention_bwd_valid_cols_kernel(const float* __restrict__ qkv, const float* __restrict__ dy,
+                                                                      const float* __restrict__ rowstat, float* __restrict__ dqkv,
+                                                                      int T, int W, int vh, int vw, int C) {
+  const int lj = blockIdx.x * 64 + threadIdx.x, h = blockIdx.y, n = blockIdx.z, NH = C / 8, V = vh * vw;
+  if (lj >= V) return;
+  const int kr = lj / vw, j = kr * W + (lj - kr * vw);
+  const float scale = 0.35355339059327373f;
+  const size_t row = ((size_t)n * T + j);
+  const f8 k = ld8(qkv + row * 3 * C + C + h * 8), v = ld8(qkv + row * 3 * C + 2 * C + h * 8);
+  const float* qbase = qkv + (size_t)n * T * 3 * C + h * 8;
+  const float* dybase = dy + (size_t)n * T * C + h * 8;
+  const float* rs = rowstat + ((size_t)n * NH + h) * V * 4;
+  f8 dk, dv;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) dk.v[e] = dv.v[e] = 0.f;
+  for (int ir = 0; ir < vh; ++ir) {
+    const float* qrow = qbase + (size_t)ir * W * 3 * C;
+    const float* dyrow = dybase + (size_t)ir * W * C;
+    const float* rsr = rs + (size_t)ir * vw * 4;
+    for (int ic = 0; ic < vw; ++ic) {
+      const f8 q = ld8(qrow + (size_t)ic * 3 * C);
+      const f8 dyo = ld8(dyrow + (size_t)ic * C);
+      const float s = dot8(q, k) * scale;
+      const float p = expf(s - rsr[4 * ic]) / rsr[4 * ic + 1];
+      const float ds = p * (dot8(dyo, v) - rsr[4 * ic + 2]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        dk.v[e] = __builtin_fmaf(ds * scale, q.v[e], dk.v[e]);
+        dv.v[e] = __builtin_fmaf(p, dyo.v[e], dv.v[e]);
+      }
+    }
+  }
+  float* o = dqkv + row * 3 * C + C + h * 8;
+  *(f32x4*)o = (f32x4){dk.v[0], dk.v[1], dk.v[2], dk.v[3]};
+  *(f32x4*)(o + 4) = (f32x4){dk.v[4], dk.v[5], dk.v[6], dk.v[7]};
+  o += C;
+  *(f32x4*)o = (f32x4){dv.v[0], dv.v[1], dv.v[2], dv.v[3]};
+  *(f32x4*)(o + 4) = (f32x4){dv.v[4], dv.v[5], dv.v[6], dv.v[7]};
+}
+
+extern "C" int dmd_attention_bwd_valid(const float* qkv, const float* y, const float* dy, float* dqkv, float* workspace, int N, int H,
+                                       int W, int valid_h, int valid_w, int C, int head_dim, dmd_stream_t stream) {
+  DMD_CHECK_ARG(qkv && y && dy && dqkv && workspace, "attention_bwd_valid: null");
+  DMD_CHECK_ARG(head_dim == 8 && C % 8 == 0 && N > 0 && H > 0 && W > 0,
+                "attention_bwd_valid: head_dim must be 8 (got %d), C %% 8 == 0 (C=%d), N, H, W > 0", head_dim, C);
+  DMD_CHECK_ARG(valid_h > 0 && valid_h <= H && valid_w > 0 && valid_w <= W, "attention_bwd_valid: valid extent %d x %d of %d x %d",
+                valid_h, valid_w, H, W);
+  hipStream_t st = (hipStream_t)stream;
+  const int T = H * W, V = valid_h * valid_w;
+  const int nbv = (V + 63) / 64, nbm = (T - V + 63) / 64;
+  hipLaunchKernelGGL(attention_bwd_valid_rows_kernel, dim3(nbv + nbm, C / 8, N), dim3(64), 0, st, qkv, y, dy, dqkv, workspace, T, W,
+                     valid_h, valid_w, C, nbv);
+  hipLaunchKernelGGL(attention_bwd_valid_cols_kernel, dim3(nbv, C / 8, N), dim3(64), 0, st, qkv, dy, (const float*)workspace, dqkv, T,
+                     W, valid_h, valid_w, C);
+  DMD_LAUNCH_CHECK();
+  return 0;
+}

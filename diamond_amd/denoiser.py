@@ -208,10 +208,18 @@ class Denoiser(nn.Module):
         cobs = obs.shape[1]
         cond4 = torch.stack((c_in, c_out, c_skip, c_noise), dim=1).detach().float().contiguous()
         cpad = (cx + cobs + 15) // 16 * 16
-        packed = torch.empty(n, h, w, cpad, device=self.device, dtype=torch.float32)
-        xc, oc = noisy_next_obs.detach().contiguous(), obs.detach().contiguous()
+        xc, oc = noisy_next_obs.detach(), obs.detach()
+        # sizes off the kernels' tile grid: the VALID EXTENT of a zero-padded buffer, as in compute_model_output; F is cropped back
+        # below, so the loss (and its gradient) covers the real pixels only
+        valid = None
+        hp, wp = E.padded_extent(h, w, im.unet._num_down)
+        if (hp, wp) != (h, w):
+            valid = (h, w)
+            xc, oc = F.pad(xc, (0, wp - w, 0, hp - h)), F.pad(oc, (0, wp - w, 0, hp - h))
+        xc, oc = xc.contiguous(), oc.contiguous()
+        packed = torch.empty(n, hp, wp, cpad, device=self.device, dtype=torch.float32)
         nv.check(nv.lib().dmd_edm_pack_input(nv.fptr(xc), nv.fptr(oc), nv.fptr(cond4), 4, float(self.cfg.sigma_data), nv.fptr(packed),
-                                             n, cx, cobs, h, w, cpad, 1, 0, nv.stream()), "dmd_edm_pack_input")
+                                             n, cx, cobs, hp, wp, cpad, 1, 0, nv.stream()), "dmd_edm_pack_input")
         # cond = cond_proj(noise_emb(c_noise) + act_emb(act))  (inner_model.py:45, blocks.py:84-87)
         # (an outer product: every element is ONE fp32 product, exactly what the (B, 1) @ (1, C) GEMM computes)
         f = 2 * math.pi * c_noise.detach().unsqueeze(1) * im.noise_emb.weight
@@ -228,7 +236,8 @@ class Denoiser(nn.Module):
         table = LinearFn.apply(im._cache, cond, w_cat, b_cat)
         if self._train_params is None:
             self._train_params = UT.trainable_unet_params(im)
-        return UT.UNetTrainFn.apply(im, packed, table, precision or UT.TRAIN_PRECISION, *self._train_params)
+        out = UT.UNetTrainFn.apply(im, packed, table, precision or UT.TRAIN_PRECISION, valid, *self._train_params)
+        return out if valid is None else out[:, :, :h, :w]
 
     def forward(self, batch):
         """Denoising loss over a segment with autoregressive refresh of the context (reference :93-122)."""

@@ -49,6 +49,7 @@ class AttnRecord:
     out: Tensor
     c: int
     head_dim: int
+    valid: Optional[Tuple[int, int]] = None  # the token grid's VALID EXTENT (dmd_attention_valid), None: all of it
 
 
 @dataclass
@@ -650,7 +651,6 @@ def conv2d(
     assert len(src_valid) == 1, f"sources with different valid extents: {src_valid}"
     sv = src_valid.pop()
     if sv is not None:
-        assert TAPE is None, "valid extents are an inference-path feature (no recorded backward)"
         valid = (sv[0] * 2, sv[1] * 2) if upsample else ((sv[0] // stride, sv[1] // stride))
         assert stride == 1 or (sv[0] % 2 == 0 and sv[1] % 2 == 0), f"stride-2 conv over an odd valid extent {sv}"
         p.valid_h, p.valid_w = valid
@@ -802,9 +802,10 @@ def attention(qkv: Act, c: int, head_dim: int = 8) -> Tensor:
     assert c3 == 3 * c
     out = torch.empty(n, h, w, c, device=qkv.t.device, dtype=torch.float32)
     if qkv.valid is not None:  # keys outside the valid extent stay out of the softmax
-        assert TAPE is None
         nv.check(nv.lib().dmd_attention_valid(nv.fptr(qkv.t), nv.fptr(out), n, h, w, qkv.valid[0], qkv.valid[1], c, head_dim, nv.stream()),
                  "dmd_attention_valid")
+        if TAPE is not None:
+            TAPE.append(AttnRecord(qkv, out, c, head_dim, qkv.valid))
         return out
     if nv.PROFILER is not None:  # QK^T and PV: 2 x (2 T^2 d) per head
         t = h * w

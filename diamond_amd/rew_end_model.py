@@ -60,7 +60,8 @@ class RewEndEncoder(nn.Module):
         self.downsamples = nn.ModuleList([nn.Identity()] + [Downsample(c) for c in channels[:-1]] + [nn.Identity()])
 
     def run(self, ctx: RunCtx, x_nhwc16: Tensor, valid: Optional[Tuple[int, int]] = None) -> E.Act:
-        """valid = (h, w): the image is that part of the zero-padded buffer (engine.padded_extent; inference only)"""
+        """valid = (h, w): the image is that part of the zero-padded buffer (engine.padded_extent); the result's valid extent is
+        the deepest level's part of its buffer"""
         x = E.conv2d([(E.Act(x_nhwc16, needs_grad=False, valid=valid), nv.PROLOGUE_NONE, None)], ctx.cache.conv_weight(self.conv_in),
                      ctx.cache.conv_bias(self.conv_in), self.conv_in.out_channels, naive=ctx.naive, w_f16=ctx.w16(self.conv_in),
                      module=self.conv_in)
@@ -209,6 +210,13 @@ class RewEndModel(nn.Module):
 
         b, t, c, h, w = obs.shape
         x = torch.cat((obs.reshape(b * t, c, h, w), next_obs.reshape(b * t, c, h, w)), dim=1).detach()
+        # sizes off the kernels' tile grid: the VALID EXTENT of a zero-padded buffer, as in predict_rew_end
+        nd = len(self.encoder.downsamples) - 2
+        hp, wp = E.padded_extent(h, w, nd)
+        valid = None if (hp, wp) == (h, w) else (h, w)
+        if valid is not None:
+            assert h % 2 ** nd == 0 and w % 2 ** nd == 0, f"RewEndModel: {h}x{w} is not a multiple of {2 ** nd} (the reference's own constraint)"
+            x = F.pad(x, (0, wp - w, 0, hp - h))
         x16 = E.nchw_to_nhwc(x, 16)
         cond = self.act_emb(act.reshape(b * t))
         if self._film is None:
@@ -224,9 +232,11 @@ class RewEndModel(nn.Module):
         precision = precision or UT.TRAIN_PRECISION
 
         def run(tab: Tensor) -> Tensor:
-            return self.encoder.run(RunCtx(self._cache, film, tab, precision=precision), x16).t
+            return self.encoder.run(RunCtx(self._cache, film, tab, precision=precision), x16, valid).t
 
         feat = UT.EncoderTrainFn.apply(run, self._cache, table, precision, *self._train_params)  # (b t, s, s, e) NHWC
+        if valid is not None:  # the deepest level's part of its buffer: the gradient outside it is zero
+            feat = feat[:, :h // 2 ** nd, :w // 2 ** nd]
         hd, e = self.cfg.lstm_dim, self.cfg.channels[-1]
         w_ih = self.lstm.weight_ih_l0
         s_ = feat.shape[1]

@@ -18,6 +18,9 @@ Per recorded convolution, with dOut the gradient of its output:
 Attention core: `dmd_attention_bwd`.  The FiLM table itself (`cond @ W_cat^T + b_cat`), the 256-wide cond MLP and the
 action embedding are a handful of tiny GEMMs: they run as torch ops under ordinary autograd, so the table gradient
 returned here flows on into the 44 AdaGroupNorm linears, `cond_proj` and `act_emb`.
+Image sizes off the kernels' tile grid record on the VALID EXTENT of a padded buffer (engine.padded_extent): the gradient
+tensors' margins are then unspecified, and every kernel of the walk reads only the extent it is given (data gradients: dy's,
+weight gradients / GroupNorm backward: their source's, attention: `dmd_attention_bwd_valid`).
 """
 from __future__ import annotations
 
@@ -72,6 +75,10 @@ def _dgrad_weights(cache: E.PackCache, conv: nn.Conv2d, c0: int, c1: int, cout_p
     return wp, w16
 
 
+def _twice(valid: Optional[Tuple[int, int]]) -> Optional[Tuple[int, int]]:
+    return None if valid is None else (2 * valid[0], 2 * valid[1])
+
+
 def _zero_stuff(dy: Tensor) -> Tensor:
     """(N, H, W, C) -> (N, 2H, 2W, C) with dy at the even positions: the transposed stride-2 convolution and its weight
     gradient are the stride-1 ones of this tensor."""
@@ -100,6 +107,8 @@ def _gn_bwd(x: Act, spec: NormSpec, da: Tensor, dskip: Optional[Tensor], identit
         return gn_bwd_sliced(lambda *a: _gn_bwd(*a, True), x, spec, da, dskip)
     p = nv.GnBwdParams()
     p.N, p.HW, p.C = n, h * w, c
+    if x.valid is not None:  # sums and the count over the valid extent, dx zero outside it
+        p.W, p.valid_h, p.valid_w = w, x.valid[0], x.valid[1]
     p.identity_activation = 1
     p.x = nv.ptr(x.t)
     p.norm = spec.to_native(x)
@@ -184,8 +193,13 @@ def backward_tape(tape: List, cache: E.PackCache, d_out: Tensor, table: Tensor, 
             ws = torch.empty(int(nv.lib().dmd_attention_bwd_workspace_floats(n, h * w, rec.c)), device=dy.device,
                              dtype=torch.float32)
             dyc = dy.contiguous()
-            nv.check(nv.lib().dmd_attention_bwd(nv.fptr(rec.qkv.t), nv.fptr(rec.out), nv.fptr(dyc), nv.fptr(dqkv),
-                                                nv.fptr(ws), n, h * w, rec.c, rec.head_dim, nv.stream()), "dmd_attention_bwd")
+            if rec.valid is not None:  # queries and keys of the valid extent only; dqkv zero outside it
+                nv.check(nv.lib().dmd_attention_bwd_valid(nv.fptr(rec.qkv.t), nv.fptr(rec.out), nv.fptr(dyc), nv.fptr(dqkv), nv.fptr(ws),
+                                                          n, h, w, rec.valid[0], rec.valid[1], rec.c, rec.head_dim, nv.stream()),
+                         "dmd_attention_bwd_valid")
+            else:
+                nv.check(nv.lib().dmd_attention_bwd(nv.fptr(rec.qkv.t), nv.fptr(rec.out), nv.fptr(dyc), nv.fptr(dqkv),
+                                                    nv.fptr(ws), n, h * w, rec.c, rec.head_dim, nv.stream()), "dmd_attention_bwd")
             grads.add(rec.qkv.t, dqkv)
             continue
         if isinstance(rec, CatRecord):  # a materialised channel concatenation (engine.concat): the gradient split by channels
@@ -211,8 +225,11 @@ def backward_tape(tape: List, cache: E.PackCache, d_out: Tensor, table: Tensor, 
                 pending_norm[_key(rec.residual.t)] = dout
             else:
                 grads.add(rec.residual.t, dout)
-        # ---- geometry of the gradient the weight / data kernels consume
+        # ---- geometry of the gradient the weight / data kernels consume.  Under a VALID EXTENT the gradient tensors' margins
+        # are unspecified (a data gradient writes the whole buffer): the data gradient reads dy as the extent of the output it is
+        # the gradient of (zero-stuffed: twice that), the weight gradient masks dy by its source's extent
         dy_k = _zero_stuff(dout) if rec.stride == 2 else dout
+        dy_valid = _twice(rec.out.valid) if rec.stride == 2 else rec.out.valid
         k = conv.kernel_size[0]
         dws: List[Tensor] = []
         db: Optional[Tensor] = None
@@ -223,7 +240,7 @@ def backward_tape(tape: List, cache: E.PackCache, d_out: Tensor, table: Tensor, 
         for si, (a, prologue, spec) in enumerate(rec.srcs):
             ci_pad = a.C
             ci_real = min(ci_pad, conv.in_channels - c0)
-            src = Act(_upsample_nearest(a.t)) if rec.upsample else a
+            src = Act(_upsample_nearest(a.t), valid=_twice(a.valid)) if rec.upsample else a
             assert not (rec.upsample and prologue != nv.PROLOGUE_NONE)
             if batch is not None:
                 step = 64 if cout > 64 and not head else dy_k.shape[-1]  # (the wgrad instances take at most 64 output channels: qkv)
@@ -246,8 +263,8 @@ def backward_tape(tape: List, cache: E.PackCache, d_out: Tensor, table: Tensor, 
                     db = db_i[:cout]
             if a.needs_grad:
                 wp, w16 = _dgrad_weights(cache, conv, c0, c0 + ci_real, cpad, use_f16)
-                da = E.conv2d([(Act(dy_k), nv.PROLOGUE_NONE, None)], wp, None, ci_real, taps=rec.taps, want_stats=False, w_f16=w16,
-                              fast_math=use_f16).t
+                da = E.conv2d([(Act(dy_k, valid=dy_valid), nv.PROLOGUE_NONE, None)], wp, None, ci_real, taps=rec.taps, want_stats=False,
+                              w_f16=w16, fast_math=use_f16).t
                 if rec.upsample:
                     da = _sum_pool2(da)
                 if prologue == nv.PROLOGUE_NONE:
@@ -278,14 +295,16 @@ def backward_tape(tape: List, cache: E.PackCache, d_out: Tensor, table: Tensor, 
 class UNetTrainFn(torch.autograd.Function):
     """F = InnerModel.run(packed_in, table) with a hand-written backward.  Inputs that carry gradients: the FiLM
     table and every parameter in `params` (the convolutions, nn.GroupNorm affines and attention projections of
-    conv_in / unet / norm_out / conv_out)."""
+    conv_in / unet / norm_out / conv_out).  valid = (h, w): the image is that part of the zero-padded packed_in
+    (InnerModel.run); F is meaningful in [:h, :w] only and the caller crops it (its gradient is zero outside)."""
 
     @staticmethod
-    def forward(ctx, inner, packed_in: Tensor, table: Tensor, precision: str, *params: Tensor) -> Tensor:
+    def forward(ctx, inner, packed_in: Tensor, table: Tensor, precision: str, valid: Optional[Tuple[int, int]],
+                *params: Tensor) -> Tensor:
         assert E.TAPE is None, "nested recording"
         E.TAPE = []
         try:
-            out = inner.run(packed_in, None, precision=precision, table=table.detach())
+            out = inner.run(packed_in, None, precision=precision, table=table.detach(), valid=valid)
             tape = E.TAPE
         finally:
             E.TAPE = None
@@ -298,7 +317,7 @@ class UNetTrainFn(torch.autograd.Function):
         pg, inv = scaled_backward(ctx.tape, ctx.inner._cache, d_out, ctx.table, use_f16=ctx.precision == "f16x2")
         ctx.tape = None  # free the saved activations
         grads = _unscale(pg, ctx.params, inv)
-        return (None, None, pg.dtable * inv, None, *grads)
+        return (None, None, pg.dtable * inv, None, None, *grads)
 
 
 def _unscale(pg: "_ParamGrads", params, inv: Tensor):

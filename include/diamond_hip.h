@@ -194,6 +194,13 @@ int dmd_attention_valid(const float* qkv, float* out, int N, int H, int W, int v
 int64_t dmd_attention_bwd_workspace_floats(int N, int T, int C);
 int dmd_attention_bwd(const float* qkv, const float* y, const float* dy, float* dqkv, float* workspace, int N, int T, int C,
                       int head_dim, dmd_stream_t stream);
+/* (ABI v11 addition) Backward of dmd_attention_valid over the (valid_h, valid_w) part of an (H, W) token grid (dmd_conv_params:
+ * VALID EXTENT): only tokens with row < valid_h and column < valid_w take part, as queries and as keys, and nothing outside the
+ * extent is read -- the margins of qkv, y and dy may hold anything, NaN / Inf included.  The dqkv rows outside the extent are
+ * written as ZERO in all three thirds.  The work is sized by the valid token count; with (valid_h, valid_w) == (H, W) the result
+ * is bitwise dmd_attention_bwd's (same summation order).  workspace: dmd_attention_bwd_workspace_floats(N, H * W, C). */
+int dmd_attention_bwd_valid(const float* qkv, const float* y, const float* dy, float* dqkv, float* workspace, int N, int H, int W,
+                            int valid_h, int valid_w, int C, int head_dim, dmd_stream_t stream);
 
 /* ---- dmd_lowres_chain: a whole chain of ResBlocks at the 8x8 level of the denoiser's U-Net in ONE launch ----
  * Replaces, for H = W = 8 and 64 channels, the launches of the deepest level of UNet.forward (reference blocks.py:232-246:
