@@ -20,7 +20,6 @@ from . import engine as E
 from . import native as nv
 from .engine import Act, NormSpec
 
-GN_GROUP_SIZE = 32
 GN_EPS = 1e-5
 ATTN_HEAD_DIM = 8
 # DIAMOND_LOWRES_CHAIN: bit 0 = the 8x8 level of the denoiser's U-Net as one dmd_lowres_chain launch, bit 1 = the 8x8 tail of
@@ -39,13 +38,13 @@ def conv1x1(cin: int, cout: int) -> nn.Conv2d:
 def _groups(c: int) -> int:
     """GroupNorm groups of a normalised width, by the reference's rule (blocks.py:27,38): max(1, C // 32) groups of C / groups
     channels.  Widths the kernels cannot normalise raise here, where the network is built, not at its first launch."""
-    g = max(1, c // GN_GROUP_SIZE)
+    g = max(1, c // nv.GN_GROUP)
     if c % g != 0:
-        raise ValueError(f"normalisation over {c} channels: the reference's {g} GroupNorm group(s) (max(1, C // {GN_GROUP_SIZE})) do not "
+        raise ValueError(f"normalisation over {c} channels: the reference's {g} GroupNorm group(s) (max(1, C // {nv.GN_GROUP})) do not "
                          f"divide {c} channels")
-    if c % 16 != 0 or (c // g) % 4 != 0 or (c % GN_GROUP_SIZE != 0 and c > 256):
+    if not E.gn_width_ok(c):
         raise ValueError(f"normalisation over {c} channels ({g} group(s) of {c / g:g}): diamond_amd's kernels need C % 16 == 0, groups "
-                         f"of a multiple of 4 channels, and C <= 256 unless C % {GN_GROUP_SIZE} == 0")
+                         f"of a multiple of 4 channels, and C <= 256 unless C % {nv.GN_GROUP} == 0")
     return g
 
 

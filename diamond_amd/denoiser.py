@@ -109,15 +109,9 @@ class Denoiser(nn.Module):
         cpad = (cx + cobs + 15) // 16 * 16
         # image sizes whose U-Net levels are not multiples of the kernels' tiles (e.g. 72x72: 72 / 36 / 18 / 9) run as the
         # VALID EXTENT of a larger zero-padded buffer (include/diamond_hip.h); the result is cropped back below
-        valid = None
-        hp, wp = E.padded_extent(h, w, self.inner_model.unet._num_down)
-        if (hp, wp) != (h, w):
-            import torch.nn.functional as F
-
-            valid = (h, w)
-            noisy_next_obs = F.pad(noisy_next_obs, (0, wp - w, 0, hp - h))
-            obs = F.pad(obs, (0, wp - w, 0, hp - h))
-            h, w = hp, wp
+        h, w = E.padded_extent(h, w, self.inner_model.unet._num_down)
+        noisy_next_obs, valid = E.pad_to_extent(noisy_next_obs, h, w)
+        obs, _ = E.pad_to_extent(obs, h, w)
         packed = torch.empty(n, h, w, cpad, device=self.device, dtype=torch.float32)
         # NOTE: pointers are only taken from tensors bound to a name -- a temporary made inside the
         # argument list would be freed (and its block re-used) before the kernel is even launched.
@@ -128,7 +122,7 @@ class Denoiser(nn.Module):
         # (table: this forward's FiLM table, if the caller computed the tables of several steps at once -- film_tables below)
         cvec = self.inner_model.cond_vector(cond, stride, act, act_head) if table is None else None
         out = self.inner_model.run(packed, cvec, naive, precision, table=table, valid=valid)
-        return out if valid is None else out[:, :, :valid[0], :valid[1]].contiguous()
+        return E.crop_to_valid(out, valid, nchw=True)
 
     @torch.no_grad()
     def wrap_model_output(self, noisy_next_obs: Tensor, model_output: Tensor, sigma: Union[Tensor, float],
@@ -208,14 +202,11 @@ class Denoiser(nn.Module):
         cobs = obs.shape[1]
         cond4 = torch.stack((c_in, c_out, c_skip, c_noise), dim=1).detach().float().contiguous()
         cpad = (cx + cobs + 15) // 16 * 16
-        xc, oc = noisy_next_obs.detach(), obs.detach()
         # sizes off the kernels' tile grid: the VALID EXTENT of a zero-padded buffer, as in compute_model_output; F is cropped back
         # below, so the loss (and its gradient) covers the real pixels only
-        valid = None
         hp, wp = E.padded_extent(h, w, im.unet._num_down)
-        if (hp, wp) != (h, w):
-            valid = (h, w)
-            xc, oc = F.pad(xc, (0, wp - w, 0, hp - h)), F.pad(oc, (0, wp - w, 0, hp - h))
+        xc, valid = E.pad_to_extent(noisy_next_obs.detach(), hp, wp)
+        oc, _ = E.pad_to_extent(obs.detach(), hp, wp)
         xc, oc = xc.contiguous(), oc.contiguous()
         packed = torch.empty(n, hp, wp, cpad, device=self.device, dtype=torch.float32)
         nv.check(nv.lib().dmd_edm_pack_input(nv.fptr(xc), nv.fptr(oc), nv.fptr(cond4), 4, float(self.cfg.sigma_data), nv.fptr(packed),

@@ -494,9 +494,8 @@ class PackCache:
     def conv_weight_f16x2(self, conv: nn.Conv2d) -> Optional[Tensor]:
         """Split-fp16 pieces of a 3x3 / 1x1 weight with 32 or 64 output channels (None for other shapes); stride 2 (Downsample)
         has the same layout -- only the few-tile kernel reads it there."""
-        if conv.out_channels not in (32, 64) or conv.kernel_size not in ((3, 3), (1, 1)) or conv.stride not in ((1, 1), (2, 2)):
-            return None
-        if conv.in_channels > (128 if conv.out_channels == 64 else 64):
+        k = conv.kernel_size[0]
+        if conv.kernel_size != (k, k) or conv.stride not in ((1, 1), (2, 2)) or not f16x2_weight_shape(conv.out_channels, conv.in_channels, k):
             return None
         return self._conv_job(conv.weight, nv.PACK_F16X2, conv.out_channels)
 
@@ -527,6 +526,12 @@ class PackCache:
         return self.get(p, "f32", lambda t: t.detach().float().contiguous())
 
 
+def f16x2_weight_shape(cout: int, cin: int, k: int) -> bool:
+    """The weight shapes that have split-fp16 pieces (the wave-specialised kernel's, dmd_conv_f16ws.hip): 3x3 / 1x1, 32 or 64 output
+    channels, at most 64 / 128 input channels.  For a data gradient: of the transposed weight."""
+    return cout in (32, 64) and cin <= (128 if cout == 64 else 64) and k in (1, 3)
+
+
 def new_stats(n: int, c: int, tiles: int, device) -> Tensor:
     return torch.empty(n, max(1, c // nv.GN_GROUP), tiles, 2, device=device, dtype=torch.float64)
 
@@ -537,6 +542,12 @@ CONV_CIN_MAX = 256  # input channels (all sources together) of ONE dmd_conv2d la
 def gn_group_size(c: int) -> int:
     """Channels per GroupNorm group of a normalised width (the reference's rule, blocks.py:27,38: max(1, C // 32) groups)."""
     return c // max(1, c // nv.GN_GROUP)
+
+
+def gn_width_ok(c: int) -> bool:
+    """mirror of dmd_gn_width_ok (csrc/dmd_common.h): a width whose GroupNorm statistics the kernels form"""
+    g = max(1, c // nv.GN_GROUP)
+    return c % 16 == 0 and c % g == 0 and (c // g) % 4 == 0 and (c % nv.GN_GROUP == 0 or c <= 256)
 
 
 def _channel_slice(a: Act, prologue: int, norm: Optional[NormSpec], c0: int, c1: int) -> Tuple[Act, int, Optional[NormSpec]]:
@@ -778,6 +789,23 @@ def padded_extent(h: int, w: int, num_down: int) -> Tuple[int, int]:
         return h, w
     m *= 2
     return (h + m - 1) // m * m, (w + m - 1) // m * m
+
+
+def pad_to_extent(x: Tensor, hp: int, wp: int) -> Tuple[Tensor, Optional[Tuple[int, int]]]:
+    """An NCHW batch as the VALID EXTENT of a zero-padded (hp, wp) buffer (zeros right and below): (buffer, (h, w)); the batch
+    itself and None where it already has that size.  The buffer size is the caller's rule (padded_extent, or the actor-critic
+    plan's grid_multiple)."""
+    h, w = x.shape[-2:]
+    if (hp, wp) == (h, w):
+        return x, None
+    return torch.nn.functional.pad(x, (0, wp - w, 0, hp - h)), (h, w)
+
+
+def crop_to_valid(t: Tensor, valid: Optional[Tuple[int, int]], nchw: bool = False) -> Tensor:
+    """The valid extent of an NHWC (or NCHW) result as a tensor of its own (valid None: all of it, as it is)."""
+    if valid is None:
+        return t
+    return (t[:, :, :valid[0], :valid[1]] if nchw else t[:, :valid[0], :valid[1]]).contiguous()
 
 
 def nchw_to_nhwc(x: Tensor, cpad: Optional[int] = None) -> Tensor:

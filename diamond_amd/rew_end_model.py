@@ -150,6 +150,15 @@ class RewEndModel(nn.Module):
             return w.detach().float().reshape(w.shape[0], e, s, s).permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
         return self._cache.get(self.lstm.weight_ih_l0, "nhwc_cols", pack)
 
+    def _pad_to_extent(self, x: Tensor) -> Tuple[Tensor, Optional[Tuple[int, int]]]:
+        """The (b t, 2c, h, w) input as the VALID EXTENT of the zero-padded buffer the encoder's levels need (engine.padded_extent)"""
+        h, w = x.shape[-2:]
+        nd = len(self.encoder.downsamples) - 2
+        x, valid = E.pad_to_extent(x, *E.padded_extent(h, w, nd))
+        assert valid is None or (h % 2 ** nd == 0 and w % 2 ** nd == 0), \
+            f"RewEndModel: {h}x{w} is not a multiple of {2 ** nd} (the reference's own constraint)"
+        return x, valid
+
     @torch.no_grad()
     def predict_rew_end(self, obs: Tensor, act: Tensor, next_obs: Tensor,
                         hx_cx: Optional[Tuple[Tensor, Tensor]] = None) -> Tuple[Tensor, Tensor, Tuple[Tensor, Tensor]]:
@@ -159,20 +168,14 @@ class RewEndModel(nn.Module):
         x = torch.cat((obs.reshape(b * t, c, h, w), next_obs.reshape(b * t, c, h, w)), dim=1)
         # sizes whose levels leave the kernels' tile grid (the reference runs any size its three stride-2 convolutions halve
         # evenly, rew_end_model.py:33: 72 -> 36 -> 18 -> 9): the VALID EXTENT of a zero-padded buffer, like the denoiser
-        nd = len(self.encoder.downsamples) - 2
-        hp, wp = E.padded_extent(h, w, nd)
-        valid = None if (hp, wp) == (h, w) else (h, w)
-        if valid is not None:
-            assert h % 2 ** nd == 0 and w % 2 ** nd == 0, f"RewEndModel: {h}x{w} is not a multiple of {2 ** nd} (the reference's own constraint)"
-            x = torch.nn.functional.pad(x, (0, wp - w, 0, hp - h))
+        x, valid = self._pad_to_extent(x)
         x16 = E.nchw_to_nhwc(x, 16)
         cond = self._cache.f32(self.act_emb.weight)[act.reshape(b * t)].contiguous()  # embedding gather (plumbing)
         if self._film is None:
             self._film = FilmTable(self.encoder)
         ctx = RunCtx(self._cache, self._film, self._film.compute(cond))
         fa = self.encoder.run(ctx, x16, valid)
-        ft = fa.t if fa.valid is None else fa.t[:, :fa.valid[0], :fa.valid[1]].contiguous()
-        feat = ft.reshape(b, t, -1)  # NHWC flatten; weight columns permuted to match
+        feat = E.crop_to_valid(fa.t, fa.valid).reshape(b, t, -1)  # NHWC flatten; weight columns permuted to match
         hd = self.cfg.lstm_dim
         if hx_cx is None:
             hx = torch.zeros(b, hd, device=dev)
@@ -212,11 +215,7 @@ class RewEndModel(nn.Module):
         x = torch.cat((obs.reshape(b * t, c, h, w), next_obs.reshape(b * t, c, h, w)), dim=1).detach()
         # sizes off the kernels' tile grid: the VALID EXTENT of a zero-padded buffer, as in predict_rew_end
         nd = len(self.encoder.downsamples) - 2
-        hp, wp = E.padded_extent(h, w, nd)
-        valid = None if (hp, wp) == (h, w) else (h, w)
-        if valid is not None:
-            assert h % 2 ** nd == 0 and w % 2 ** nd == 0, f"RewEndModel: {h}x{w} is not a multiple of {2 ** nd} (the reference's own constraint)"
-            x = F.pad(x, (0, wp - w, 0, hp - h))
+        x, valid = self._pad_to_extent(x)
         x16 = E.nchw_to_nhwc(x, 16)
         cond = self.act_emb(act.reshape(b * t))
         if self._film is None:

@@ -4,7 +4,7 @@ differentiates blocks.py / inner_model.py).
 
 Design: the inference forward (`InnerModel.run`) is executed unchanged while `engine.TAPE` records every conv /
 attention launch; ONE `torch.autograd.Function` spans the whole network and its backward walks the tape in reverse.
-Per recorded convolution, with dOut the gradient of its output:
+Per recorded convolution, with dOut the gradient of its output (the launches themselves: grad_ops.py):
   * bias / weight gradient  -> `dmd_conv2d_wgrad` per source (the activated input SiLU(GN(x)*..) is recomputed from x and
     its statistics while staging: nothing but the layer inputs was saved);
   * data gradient           -> `dmd_conv2d` on the flipped / transposed weight slice of that source (split-fp16 MFMA
@@ -24,15 +24,14 @@ weight gradients / GroupNorm backward: their source's, attention: `dmd_attention
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import Tensor, nn
 
 from . import engine as E
+from . import grad_ops as G
 from . import native as nv
-from .ac_native import WgradBatch, _gn_bwd_instance, _gn_silu_bwd, _transposed, _wgrad, gn_bwd_sliced
 from .engine import Act, AttnRecord, CatRecord, ConvRecord, NormSpec
 
 TRAIN_PRECISION = "f16x2"  # arithmetic of the forward, dgrad and wgrad convolutions (split-fp16 operands, fp32 accumulate); "f32" = exact
@@ -62,19 +61,6 @@ class _Grads:
         return self.g.get(_key(t))
 
 
-def _dgrad_weights(cache: E.PackCache, conv: nn.Conv2d, c0: int, c1: int, cout_pad: Optional[int], use_f16: bool):
-    """Packed weight of the transposed convolution restricted to input channels [c0, c1) of `conv`:
-    w_t[ci - c0][co][ky][kx] = w[co][ci][K-1-ky][K-1-kx]; co zero-padded to `cout_pad` (conv_out: 3 -> 16)."""
-
-    wp = cache.dgrad_weight(conv, c0, c1, cout_pad or 0)
-    w16 = None
-    ci, co = c1 - c0, cout_pad or conv.out_channels
-    k = conv.kernel_size[0]
-    if use_f16 and ci in (32, 64) and co <= (128 if ci == 64 else 64) and k in (1, 3):
-        w16 = cache.dgrad_weight(conv, c0, c1, cout_pad or 0, f16x2=True)
-    return wp, w16
-
-
 def _twice(valid: Optional[Tuple[int, int]]) -> Optional[Tuple[int, int]]:
     return None if valid is None else (2 * valid[0], 2 * valid[1])
 
@@ -95,32 +81,6 @@ def _upsample_nearest(x: Tensor) -> Tensor:
 def _sum_pool2(g: Tensor) -> Tensor:
     n, h, w, c = g.shape
     return g.reshape(n, h // 2, 2, w // 2, 2, c).sum(dim=(2, 4)).contiguous()
-
-
-def _gn_bwd(x: Act, spec: NormSpec, da: Tensor, dskip: Optional[Tensor], identity: bool):
-    import ctypes as C
-
-    if not identity:
-        return _gn_silu_bwd(x, spec, da, dskip)
-    n, h, w, c = x.shape
-    if not _gn_bwd_instance(c):  # (never at the default configuration)
-        return gn_bwd_sliced(lambda *a: _gn_bwd(*a, True), x, spec, da, dskip)
-    p = nv.GnBwdParams()
-    p.N, p.HW, p.C = n, h * w, c
-    if x.valid is not None:  # sums and the count over the valid extent, dx zero outside it
-        p.W, p.valid_h, p.valid_w = w, x.valid[0], x.valid[1]
-    p.identity_activation = 1
-    p.x = nv.ptr(x.t)
-    p.norm = spec.to_native(x)
-    p.da = nv.fptr(da)
-    p.dskip = nv.fptr(dskip)
-    dx = torch.empty_like(x.t)
-    ws = torch.empty(int(nv.lib().dmd_gn_bwd_workspace_bytes(n, h * w, c)), device=da.device, dtype=torch.uint8)
-    dmul = torch.empty(n, c, device=da.device, dtype=torch.float32)
-    dadd = torch.empty(n, c, device=da.device, dtype=torch.float32)
-    p.dx, p.workspace, p.dmul, p.dadd = nv.ptr(dx), nv.ptr(ws), nv.ptr(dmul), nv.ptr(dadd)
-    nv.check(nv.lib().dmd_gn_silu_bwd(C.byref(p), nv.stream()), "dmd_gn_silu_bwd")
-    return dx, dmul, dadd
 
 
 class _ParamGrads:
@@ -175,7 +135,7 @@ def backward_tape(tape: List, cache: E.PackCache, d_out: Tensor, table: Tensor, 
     pending_norm: Dict[int, Tensor] = {}  # gradient w.r.t. GN_affine(x) handed over by a residual_norm consumer
     # the reductions of ALL weight gradients as one launch per 32 at the end (bit-identical sums), every source / 64-channel piece
     # of a convolution writing its slice of ONE OIHW tensor; DIAMOND_WGRAD_DEFER=0: reduced per call and concatenated, as before
-    batch = WgradBatch() if os.environ.get("DIAMOND_WGRAD_DEFER", "1") == "1" else None
+    batch = G.wgrad_batch()
     if out_nhwc is None:
         last = tape[-1]
         assert isinstance(last, ConvRecord) and last.out_nchw, "the tape must end with the NCHW head convolution"
@@ -242,27 +202,22 @@ def backward_tape(tape: List, cache: E.PackCache, d_out: Tensor, table: Tensor, 
             ci_real = min(ci_pad, conv.in_channels - c0)
             src = Act(_upsample_nearest(a.t), valid=_twice(a.valid)) if rec.upsample else a
             assert not (rec.upsample and prologue != nv.PROLOGUE_NONE)
-            if batch is not None:
-                step = 64 if cout > 64 and not head else dy_k.shape[-1]  # (the wgrad instances take at most 64 output channels: qkv)
-                for o in range(0, dy_k.shape[-1], step):
-                    dy_o = dy_k if step == dy_k.shape[-1] else dy_k[..., o:o + step].contiguous()
-                    _wgrad(src, prologue, spec, dy_o, rec.taps, ci_real, split=use_f16, batch=batch, dw_out=dw_all[o:o + step], c0=c0,
-                           db_out=db[o:o + step] if si == 0 else None)
-            elif cout > 64 and not head:  # qkv (192 channels): the wgrad instances take at most 64 output channels
-                parts = []
-                for o in range(0, cout, 64):
-                    dwp, dbp = _wgrad(src, prologue, spec, dy_k[..., o:o + 64].contiguous(), rec.taps, ci_real, split=use_f16)
-                    parts.append((dwp, dbp))
-                dw_i = torch.cat([p_[0] for p_ in parts], dim=0)
-                db_i = torch.cat([p_[1] for p_ in parts], dim=0)
-            else:
-                dw_i, db_i = _wgrad(src, prologue, spec, dy_k, rec.taps, ci_real, split=use_f16)
-            if batch is None:
+            step = 64 if cout > 64 and not head else dy_k.shape[-1]  # (the wgrad instances take at most 64 output channels: qkv)
+            parts = []
+            for o in range(0, dy_k.shape[-1], step):
+                dy_o = dy_k if step == dy_k.shape[-1] else dy_k[..., o:o + step].contiguous()
+                if batch is not None:
+                    G.wgrad(src, prologue, spec, dy_o, rec.taps, ci_real, split=use_f16, batch=batch, dw_out=dw_all[o:o + step], c0=c0,
+                            db_out=db[o:o + step] if si == 0 else None)
+                else:
+                    parts.append(G.wgrad(src, prologue, spec, dy_o, rec.taps, ci_real, split=use_f16))
+            if batch is None:  # (reduced per call; the 64-row pieces of a gradient concatenated)
+                dw_i, db_i = parts[0] if len(parts) == 1 else (torch.cat([p_[i] for p_ in parts], dim=0) for i in (0, 1))
                 dws.append(dw_i[:cout])
                 if si == 0:
                     db = db_i[:cout]
             if a.needs_grad:
-                wp, w16 = _dgrad_weights(cache, conv, c0, c0 + ci_real, cpad, use_f16)
+                wp, w16 = G.dgrad_weights(cache, conv, c0, c0 + ci_real, cpad or 0, f16x2=use_f16)
                 da = E.conv2d([(Act(dy_k, valid=dy_valid), nv.PROLOGUE_NONE, None)], wp, None, ci_real, taps=rec.taps, want_stats=False,
                               w_f16=w16, fast_math=use_f16).t
                 if rec.upsample:
@@ -273,7 +228,7 @@ def backward_tape(tape: List, cache: E.PackCache, d_out: Tensor, table: Tensor, 
                     identity = prologue == nv.PROLOGUE_NORM
                     if identity and _key(a.t) in pending_norm:
                         da = da + pending_norm.pop(_key(a.t))
-                    dx, dmul, dadd = _gn_bwd(a, spec, da, grads.pop(a.t), identity)
+                    dx, (dmul, dadd) = G.gn_bwd(a, spec, da, grads.pop(a.t), identity)
                     grads.g[_key(a.t)] = dx  # dx already contains the gradient accumulated so far (dskip)
                     pg.norm_terms(spec, dmul, dadd)
             c0 += ci_real
@@ -339,14 +294,10 @@ def _unscale(pg: "_ParamGrads", params, inv: Tensor):
 
 def scaled_backward(tape: List, cache: E.PackCache, d_out: Tensor, table: Tensor, use_f16: bool,
                     out_nhwc: Optional[Tensor] = None) -> Tuple[_ParamGrads, Tensor]:
-    """backward_tape on d_out * 2^k with the largest entry O(1); returns (gradients of the scaled problem, 2^-k).
-    The backward is linear in d_out, so scaling back is exact in fp32.  Loss gradients are ~1e-5 and smaller; the
-    split-fp16 dgrad operands have an absolute resolution floor of 2^-25 (dmd_conv_f16ws.hip) that unscaled gradients
-    would sit on."""
-    d_out = d_out.detach().float()
-    amax = d_out.abs().amax()
-    k = torch.where(amax > 0, torch.floor(-torch.log2(amax.clamp_min(1e-37))), torch.zeros_like(amax)).clamp(-120, 120)
-    return backward_tape(tape, cache, d_out * torch.exp2(k), table, use_f16, out_nhwc), torch.exp2(-k)
+    """backward_tape on d_out * 2^k with the largest entry O(1) (grad_ops.pow2_scaled); returns (gradients of the scaled
+    problem, 2^-k)."""
+    d_scaled, inv = G.pow2_scaled(d_out)
+    return backward_tape(tape, cache, d_scaled, table, use_f16, out_nhwc), inv
 
 
 class EncoderTrainFn(torch.autograd.Function):

@@ -377,7 +377,7 @@ WGRAD_CASES = [
 @pytest.mark.parametrize("split", [False, True], ids=["exact", "f16x2"])
 @pytest.mark.parametrize("case", WGRAD_CASES, ids=[c[0] for c in WGRAD_CASES])
 def test_conv_wgrad(case, split, max_wg, dmd_env):
-    from diamond_amd import ac_native as A, engine as E
+    from diamond_amd import engine as E, grad_ops as G
 
     dmd_env(DIAMOND_WGRAD_MAX_WG=max_wg)
     name, n, h, w, cin, cin_real, cout, taps, prologue = case
@@ -399,7 +399,7 @@ def test_conv_wgrad(case, split, max_wg, dmd_env):
     xa = make_act(x)
     spec = E.NormSpec(mul=gamma.float().to(DEV), add=beta.float().to(DEV)) if prologue else None
     dyd = to_nhwc(dy.float()).to(DEV)
-    dw, db = A._wgrad(xa, prologue, spec, dyd, taps, cin_real, split=split)
+    dw, db = G.wgrad(xa, prologue, spec, dyd, taps, cin_real, split=split)
     torch.cuda.synchronize()
     assert rel_err(dw, wgt.grad) < 2e-5, f"{name}: dW rel err {rel_err(dw, wgt.grad):.3e}"
     assert rel_err(db, bias.grad) < 2e-5, f"{name}: db rel err {rel_err(db, bias.grad):.3e}"
@@ -410,7 +410,7 @@ def test_conv_wgrad(case, split, max_wg, dmd_env):
 def test_conv_wgrad_two_roles_same_bits(shape, max_wg, dmd_env):
     """wgrad_ps_kernel (producer / consumer waves; the split-fp16 default) against wgrad_kernel<G, true> (DIAMOND_WGRAD_PS=0) on a
     source without prologue: the same pixels at the same k of every MFMA in the same order -- the same bits on the hardware too."""
-    from diamond_amd import ac_native as A
+    from diamond_amd import grad_ops as G
 
     n, h, w, cin, cout, taps = shape
     g = torch.Generator().manual_seed(n * 31 + cin)
@@ -419,7 +419,7 @@ def test_conv_wgrad_two_roles_same_bits(shape, max_wg, dmd_env):
     got = []
     for ps in (1, 0):
         dmd_env(DIAMOND_WGRAD_PS=ps, DIAMOND_WGRAD_MAX_WG=max_wg)
-        dw, db = A._wgrad(E_act(x), 0, None, dy, taps, cin, split=True)
+        dw, db = G.wgrad(E_act(x), 0, None, dy, taps, cin, split=True)
         torch.cuda.synchronize()
         got.append((dw.cpu(), db.cpu()))
     assert torch.isfinite(got[0][0]).all() and torch.equal(got[0][0], got[1][0])
@@ -435,7 +435,7 @@ def test_conv_wgrad_run_to_run(shape):
     of the staging compiled as straight-line code, the two-workgroups-per-CU shapes -- 32 or 16 input channels to 32 outputs, 3 x 3 --
     gave three answers in three runs, profiles/r06n_wgrad_race.txt; the second assert pins the many-workgroup plan to the
     one-workgroup-per-CU plan of the same launch.)"""
-    from diamond_amd import ac_native as A, engine as E
+    from diamond_amd import engine as E, grad_ops as G
 
     n, h, w, cin, cout, taps, prologue = shape
     g = torch.Generator().manual_seed(n + cin)
@@ -445,7 +445,7 @@ def test_conv_wgrad_run_to_run(shape):
     spec = E.NormSpec(mul=(torch.randn(cin, generator=g) * 0.2 + 1).to(DEV), add=(torch.randn(cin, generator=g) * 0.2).to(DEV)) if prologue else None
     first = None
     for _ in range(12):
-        dw, db = A._wgrad(xa, prologue, spec, dy, taps, cin, split=True)
+        dw, db = G.wgrad(xa, prologue, spec, dy, taps, cin, split=True)
         torch.cuda.synchronize()
         if first is None:
             first = (dw.clone(), db.clone())
@@ -457,7 +457,7 @@ def test_conv_wgrad_run_to_run(shape):
         os.environ["DIAMOND_WGRAD_MAX_WG"] = "256"
         reload_dmd_env()
         try:
-            dw1, db1 = A._wgrad(xa, prologue, spec, dy, taps, cin, split=True)
+            dw1, db1 = G.wgrad(xa, prologue, spec, dy, taps, cin, split=True)
             torch.cuda.synchronize()
         finally:
             del os.environ["DIAMOND_WGRAD_MAX_WG"]
@@ -473,7 +473,7 @@ def E_act(t):
 
 @pytest.mark.parametrize("n,c,h,w,skip", [(3, 32, 16, 16, True), (2, 64, 8, 8, False), (2, 32, 64, 64, True), (2, 64, 24, 40, True)])
 def test_gn_silu_bwd(n, c, h, w, skip):
-    from diamond_amd import ac_native as A, engine as E
+    from diamond_amd import engine as E, grad_ops as G
 
     g = torch.Generator().manual_seed(n + c + h)
     x = (torch.randn(n, c, h, w, generator=g, dtype=torch.float64) * 1.7 + 0.4).requires_grad_(True)
@@ -489,7 +489,7 @@ def test_gn_silu_bwd(n, c, h, w, skip):
     spec = E.NormSpec(mul=gamma.detach().float().to(DEV), add=beta.detach().float().to(DEV))
     dad = to_nhwc(da.float()).to(DEV)
     dsd = to_nhwc(dskip.float()).to(DEV) if skip else None
-    dx, dmul, dadd = A._gn_silu_bwd(xa, spec, dad, dsd)
+    dx, (dmul, dadd) = G.gn_bwd(xa, spec, dad, dsd)
     torch.cuda.synchronize()
     assert rel_err(dx.permute(0, 3, 1, 2), x.grad) < 2e-5
     assert rel_err(dmul.sum(0), gamma.grad) < 2e-5
@@ -497,14 +497,14 @@ def test_gn_silu_bwd(n, c, h, w, skip):
 
 
 def test_maxpool_bwd():
-    from diamond_amd import ac_native as A
+    from diamond_amd import ac_native as A, grad_ops as G
 
     g = torch.Generator().manual_seed(11)
     x = torch.randn(3, 32, 16, 24, generator=g).requires_grad_(True)
     dp = torch.randn(3, 32, 8, 12, generator=g)
     F.max_pool2d(x, 2).backward(dp)
     pooled, arg = A._maxpool(to_nhwc(x.detach()).to(DEV))
-    dx = A._maxpool_bwd(to_nhwc(dp).to(DEV), arg)
+    dx = G.maxpool_bwd(to_nhwc(dp).to(DEV), arg)
     assert torch.equal(dx.cpu().permute(0, 3, 1, 2), x.grad)
 
 

@@ -127,7 +127,7 @@ def test_attention_and_gn_stats_valid_extent():
                                                      (32, 64, 1, (18, 18), (24, 24)), (64, 64, 9, (9, 9), (16, 16)), (16, 32, 9, (72, 72), (80, 80))])
 def test_wgrad_valid_extent(cin, cout, taps, valid, buf, split):
     """dW / db of a convolution whose input and output exist on the valid extent only: margins of x AND of dy are garbage"""
-    from diamond_amd import ac_native as A, engine as E
+    from diamond_amd import engine as E, grad_ops as G
 
     g = torch.Generator().manual_seed(cin + cout + taps + valid[0])
     n, (vh, vw), k = 3, valid, 3 if taps == 9 else 1
@@ -145,14 +145,14 @@ def test_wgrad_valid_extent(cin, cout, taps, valid, buf, split):
     F.conv2d(a, wgt, bias, padding=1 if k == 3 else 0).backward(dy)
     xa = E.gn_stats(_embed(x.float(), *buf), valid) if prologue else E.Act(_embed(x.float(), *buf), valid=valid)
     spec = E.NormSpec(mul=gamma.float().to(DEV), add=beta.float().to(DEV)) if prologue else None
-    dw, db = A._wgrad(xa, prologue, spec, _embed(dy.float(), *buf, fill=-53.0), taps, cin, split=split)
+    dw, db = G.wgrad(xa, prologue, spec, _embed(dy.float(), *buf, fill=-53.0), taps, cin, split=split)
     assert rel_err(dw, wgt.grad) < 2e-5 and rel_err(db, bias.grad) < 2e-5, (rel_err(dw, wgt.grad), rel_err(db, bias.grad))
 
 
 @pytest.mark.parametrize("c,valid,buf,skip", [(32, (36, 36), (40, 40), True), (64, (9, 9), (16, 16), False), (32, (18, 20), (24, 24), True)])
 def test_gn_silu_bwd_valid_extent(c, valid, buf, skip):
     """sums, count and dx over the valid extent; dx is ZERO outside it (what the max-pool backward / next wgrad rely on)"""
-    from diamond_amd import ac_native as A, engine as E
+    from diamond_amd import engine as E, grad_ops as G
 
     g = torch.Generator().manual_seed(c + valid[0])
     n, (vh, vw) = 2, valid
@@ -166,7 +166,7 @@ def test_gn_silu_bwd_valid_extent(c, valid, buf, skip):
     tot.backward()
     xa = E.gn_stats(_embed(x.detach().float(), *buf), valid)
     spec = E.NormSpec(mul=gamma.detach().float().to(DEV), add=beta.detach().float().to(DEV))
-    dx, dmul, dadd = A._gn_silu_bwd(xa, spec, _embed(da.float(), *buf, fill=91.0), _embed(dskip.float(), *buf, fill=-17.0) if skip else None)
+    dx, (dmul, dadd) = G.gn_bwd(xa, spec, _embed(da.float(), *buf, fill=91.0), _embed(dskip.float(), *buf, fill=-17.0) if skip else None)
     assert rel_err(dx[:, :vh, :vw].permute(0, 3, 1, 2), x.grad) < 2e-5
     assert rel_err(dmul.sum(0), gamma.grad) < 2e-5 and rel_err(dadd.sum(0), beta.grad) < 2e-5
     outside = dx.clone()

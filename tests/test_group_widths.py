@@ -130,7 +130,7 @@ def test_groupnorm_silu_backward_vs_fp64(c, valid, film, backend):
     """dmd_gn_silu_bwd on the general groups: dx (+ the skip gradient), d mul, d add of GroupNorm + affine (nn.GroupNorm) or
     GroupNorm + FiLM (AdaGroupNorm: y = xn * (1 + scale) + shift) + SiLU, with and without a valid extent, against autograd in fp64"""
     from diamond_amd import engine as E
-    from diamond_amd.ac_native import _gn_silu_bwd
+    from diamond_amd.grad_ops import gn_bwd
     from diamond_amd.engine import NormSpec
 
     g = torch.Generator().manual_seed(300 + c)
@@ -154,7 +154,7 @@ def test_groupnorm_silu_backward_vs_fp64(c, valid, film, backend):
     with ctx:
         xa = E.gn_stats(on(x), (vh, vw) if valid else None)
         spec = NormSpec(mul=on(mul), add=on(add), mul_stride=c if film else 0, add_stride=c if film else 0, plus_one=film)
-        dx, dmul, dadd = _gn_silu_bwd(xa, spec, on(da), on(dskip))
+        dx, (dmul, dadd) = gn_bwd(xa, spec, on(da), on(dskip))
     dx = dx.cpu().double()
     assert rel(dx[:, :vh, :vw], xv.grad.permute(0, 2, 3, 1) + dskip[:, :vh, :vw].double()) < 1e-5
     if valid:
@@ -171,7 +171,7 @@ def test_weight_gradient_normalised_source_vs_fp64(c, taps, split, backend):
     """dmd_conv2d_wgrad's general-group instances (one whole group per launch, WgradGeomGN): the GroupNorm + affine + SiLU of the
     source recomputed while staging, dW and db against fp64 torch"""
     from diamond_amd import engine as E
-    from diamond_amd.ac_native import _wgrad
+    from diamond_amd.grad_ops import wgrad
     from diamond_amd import native as nv
     from diamond_amd.engine import NormSpec
 
@@ -188,7 +188,7 @@ def test_weight_gradient_normalised_source_vs_fp64(c, taps, split, backend):
     ctx, dev = _backend(backend)
     on = lambda t: t.contiguous().to(dev)
     with ctx:
-        dw, db = _wgrad(E.gn_stats(on(x)), nv.PROLOGUE_NORM_SILU, NormSpec(mul=on(gamma), add=on(beta)), on(dy), taps, c, split=split)
+        dw, db = wgrad(E.gn_stats(on(x)), nv.PROLOGUE_NORM_SILU, NormSpec(mul=on(gamma), add=on(beta)), on(dy), taps, c, split=split)
     tol = 2e-5 if split else 2e-6
     assert rel(dw.cpu(), wt.grad) < tol and rel(db.cpu(), bt.grad) < tol, (rel(dw.cpu(), wt.grad), rel(db.cpu(), bt.grad))
 

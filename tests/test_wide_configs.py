@@ -1,7 +1,7 @@
 """Networks WIDER than the reference's one published configuration (tests/wide_configs.py): the reference's constructors take any
 `channels` / `depths` lists (models/blocks.py:183-222, rew_end_model.py:93-133, actor_critic.py:101-113), the kernels are
 instantiated for the default configuration's shapes, and the host covers the rest by decomposition (engine._conv2d_wide: input
-channels in runs of <= 256; ac_native._wgrad_tiled: the (Cout, Cin) plane in 64 x 64 tiles; ac_native.gn_bwd_sliced: whole
+channels in runs of <= 256; grad_ops._wgrad_tiled: the (Cout, Cin) plane in 64 x 64 tiles; grad_ops.gn_bwd_sliced: whole
 GroupNorm groups).  Held against fixtures produced by EXECUTING THE REFERENCE on the same configurations
 (tests/golden/make_golden.py --wide -> tests/golden/wide.pt), at the bars of the default configuration's tests (1e-4).
 

@@ -3,7 +3,7 @@ import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import torch
-from diamond_amd import ac_native as A, engine as E, native as nv
+from diamond_amd import engine as E, grad_ops as G, native as nv
 
 
 def setcap(c):
@@ -19,11 +19,11 @@ for prologue in (0, 1, 2):
     xa = E.gn_stats(x) if prologue else E.Act(x)
     spec = E.NormSpec(mul=(torch.randn(cin, generator=g) * 0.2 + 1).to(DEV), add=(torch.randn(cin, generator=g) * 0.2).to(DEV)) if prologue else None
     setcap("256")
-    ref, refb = A._wgrad(xa, prologue, spec, dy, taps, cin, split=True)
+    ref, refb = G.wgrad(xa, prologue, spec, dy, taps, cin, split=True)
     torch.cuda.synchronize()
     for cap in ("256", "384") + ("512",) * int(os.environ.get("RACE_REPS", "3")):
         setcap(cap)
-        dw, db = A._wgrad(xa, prologue, spec, dy, taps, cin, split=True)
+        dw, db = G.wgrad(xa, prologue, spec, dy, taps, cin, split=True)
         torch.cuda.synchronize()
         d = (dw - ref)
         bad = d != 0

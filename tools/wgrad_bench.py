@@ -6,7 +6,7 @@ usage: python tools/wgrad_bench.py [wgrad|gn|all] [reps] [only: a substring of t
 import sys, os
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
-from diamond_amd import ac_native as A, engine as E, native as nv
+from diamond_amd import engine as E, grad_ops as G, native as nv
 
 what = sys.argv[1] if len(sys.argv) > 1 else "all"
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 30
@@ -42,7 +42,7 @@ if what in ("wgrad", "all"):
         dy = torch.randn(n, h, h, cout, device=dev, generator=g)
         xa = E.gn_stats(x)
         spec = E.NormSpec(mul=torch.randn(cin, device=dev, generator=g) * 0.2 + 1, add=torch.randn(cin, device=dev, generator=g) * 0.2) if pro else None
-        us, (dw, db) = timed(lambda: A._wgrad(xa, pro, spec, dy, taps, cin, split=True))
+        us, (dw, db) = timed(lambda: G.wgrad(xa, pro, spec, dy, taps, cin, split=True))
         flop = 2.0 * taps * cin * cout * n * h * h
         print(f"wgrad {name:22s} {us:8.1f} us  {flop/us/1e6:7.1f} TFLOP/s algorithmic   sum {float(dw.double().sum()):+.9e} abs {float(dw.double().abs().sum()):.9e}", flush=True)
         del x, dy, xa
@@ -57,7 +57,7 @@ if what in ("gn", "all"):
         dskip = torch.randn(n, h, h, c, device=dev, generator=g)
         xa = E.gn_stats(x)
         spec = E.NormSpec(mul=torch.randn(c, device=dev, generator=g) * 0.2 + 1, add=torch.randn(c, device=dev, generator=g) * 0.2)
-        us, (dx, dmul, dadd) = timed(lambda: A._gn_silu_bwd(xa, spec, da, dskip))
+        us, (dx, (dmul, dadd)) = timed(lambda: G.gn_bwd(xa, spec, da, dskip))
         mb = 4.0 * x.numel() * 4 / 1e6
         print(f"gn_bwd {name:22s} {us:8.1f} us  {mb/us*1e3:7.1f} GB/s algorithmic ({mb:.0f} MB)   sum {float(dx.double().sum()):+.9e} dmul {float(dmul.double().sum()):+.9e}", flush=True)
         del x, da, dskip, xa
