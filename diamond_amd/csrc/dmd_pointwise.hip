@@ -766,3 +766,108 @@ extern "C" int dmd_categorical_sample(const float* logits, const float* expo, in
   DMD_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- reward / end training loss (reference rew_end_model.py:72-88) as ONE launch of one workgroup ------------------------------
+// logits (R, 5): columns 0-2 the reward head, 3-4 the end head.  Over the rows with mask != 0 (n of them):
+//   losses[0] = mean cross-entropy of the reward head against class sign(rew) + 1 (-0.0 and 0.0: class 1)
+//   losses[1] = mean cross-entropy of the end head against class (end != 0)
+//   dlogits   = d(losses[0] + losses[1]) / dlogits = (softmax - onehot) / n per head, exact zeros on the other rows
+//   counts    = the two confusion matrices [true][argmax] (3 x 3, then 2 x 2; ties: the lowest index)
+// n == 0: 0.0 / 0 = NaN losses (the mean of an empty selection), dlogits and counts all zero.
+// Deterministic: thread t walks rows t, t + 256, ... in ascending order (fp64 loss sums, integer counts), the 256 partials are
+// added in ascending thread order from LDS; no atomics.  log-soft-max in fp32 with the row maximum subtracted.
+#define DMD_REL_THREADS 256
+__global__ __launch_bounds__(DMD_REL_THREADS) void rew_end_loss_kernel(const float* __restrict__ logits, const float* __restrict__ rew,
+                                                                       const int64_t* __restrict__ end, const uint8_t* __restrict__ mask,
+                                                                       float* __restrict__ losses, float* __restrict__ dlogits,
+                                                                       int64_t* __restrict__ counts, int R) {
+  __shared__ double lsum[2][DMD_REL_THREADS];
+  __shared__ int cnt[14][DMD_REL_THREADS];  // rows 0-12: the confusion counts, row 13: masked rows
+  __shared__ int n_all;
+  const int tid = threadIdx.x;
+  int mine = 0;
+  for (int r = tid; r < R; r += DMD_REL_THREADS) mine += mask[r] != 0 ? 1 : 0;
+  cnt[13][tid] = mine;
+  __syncthreads();
+  if (tid == 0) {
+    int n = 0;
+    for (int i = 0; i < DMD_REL_THREADS; ++i) n += cnt[13][i];
+    n_all = n;
+  }
+  __syncthreads();
+  const int n = n_all;
+  const float nf = (float)n;
+  double s_rew = 0.0, s_end = 0.0;
+  int c[13];
+#pragma unroll
+  for (int k = 0; k < 13; ++k) c[k] = 0;
+  for (int r = tid; r < R; r += DMD_REL_THREADS) {
+    float* d = dlogits + (size_t)r * 5;
+    if (mask[r] == 0) {
+#pragma unroll
+      for (int k = 0; k < 5; ++k) d[k] = 0.f;
+      continue;
+    }
+    const float* l = logits + (size_t)r * 5;
+    const float l0 = l[0], l1 = l[1], l2 = l[2], l3 = l[3], l4 = l[4];
+    const float rv = rew[r];
+    const int tr = rv > 0.f ? 2 : (rv < 0.f ? 0 : 1);
+    const int te = end[r] != 0 ? 1 : 0;
+    {  // reward head
+      const float m = fmaxf(l0, fmaxf(l1, l2));
+      const float e0 = expf(l0 - m), e1 = expf(l1 - m), e2 = expf(l2 - m);
+      const float s = e0 + e1 + e2;
+      const float lt = tr == 0 ? l0 : (tr == 1 ? l1 : l2);
+      s_rew += (double)(logf(s) - (lt - m));
+      d[0] = (e0 / s - (tr == 0 ? 1.f : 0.f)) / nf;
+      d[1] = (e1 / s - (tr == 1 ? 1.f : 0.f)) / nf;
+      d[2] = (e2 / s - (tr == 2 ? 1.f : 0.f)) / nf;
+      int pr = 0;
+      float best = l0;
+      if (l1 > best) {
+        best = l1;
+        pr = 1;
+      }
+      if (l2 > best) pr = 2;
+      const int cell = tr * 3 + pr;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) c[k] += cell == k ? 1 : 0;
+    }
+    {  // end head
+      const float m = fmaxf(l3, l4);
+      const float e0 = expf(l3 - m), e1 = expf(l4 - m);
+      const float s = e0 + e1;
+      const float lt = te == 0 ? l3 : l4;
+      s_end += (double)(logf(s) - (lt - m));
+      d[3] = (e0 / s - (te == 0 ? 1.f : 0.f)) / nf;
+      d[4] = (e1 / s - (te == 1 ? 1.f : 0.f)) / nf;
+      const int cell = te * 2 + (l4 > l3 ? 1 : 0);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) c[9 + k] += cell == k ? 1 : 0;
+    }
+  }
+  lsum[0][tid] = s_rew;
+  lsum[1][tid] = s_end;
+#pragma unroll
+  for (int k = 0; k < 13; ++k) cnt[k][tid] = c[k];
+  __syncthreads();
+  if (tid < 13) {
+    int64_t a = 0;
+    for (int i = 0; i < DMD_REL_THREADS; ++i) a += cnt[tid][i];
+    counts[tid] = a;
+  } else if (tid < 15) {
+    double a = 0.0;
+    for (int i = 0; i < DMD_REL_THREADS; ++i) a += lsum[tid - 13][i];
+    losses[tid - 13] = (float)(a / (double)n);
+  }
+}
+
+extern "C" int dmd_rew_end_loss(const float* logits, const float* rew, const int64_t* end, const uint8_t* mask, float* losses,
+                                float* dlogits, int64_t* counts, int R, dmd_stream_t stream) {
+  DMD_CHECK_ARG(logits && rew && end && mask && losses && dlogits && counts, "rew_end_loss: null");
+  DMD_CHECK_ARG(R >= 1 && R <= (1 << 20), "rew_end_loss: R %d (1 ... 2^20 rows)", R);
+  hipLaunchKernelGGL(rew_end_loss_kernel, dim3(1), dim3(DMD_REL_THREADS), 0, (hipStream_t)stream, logits, rew, end, mask, losses, dlogits,
+                     counts, R);
+  DMD_LAUNCH_CHECK();
+  return 0;
+}

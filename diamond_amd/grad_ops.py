@@ -7,6 +7,7 @@ backward of the U-Net and the reward / end encoder (unet_train.py):
   dgrad_weights   the packed weights of the data gradient, which is dmd_conv2d (engine.conv2d) on the flipped / transposed weight
   gn_bwd          dmd_gn_silu_bwd (GroupNorm + FiLM / affine + SiLU or identity)
   pow2_scaled     the 2^k scaling both backward passes run under
+  rew_end_loss    dmd_rew_end_loss (the reward / end model's two cross-entropies, their gradient and confusion matrices: one launch)
 
 Plumbing only, like engine.py; the arithmetic ("f16x2" / "f32") is its callers' choice and arrives as an argument.
 """
@@ -276,3 +277,41 @@ def gn_bwd(x: Act, spec: NormSpec, da: Tensor, dskip: Optional[Tensor], identity
         nv.PROFILER.annotate("dmd_gn_silu_bwd", 0.0, 4.0 * x.t.numel() * (3 + (dskip is not None)))
     nv.check(nv.lib().dmd_gn_silu_bwd(C.byref(p), nv.stream()), "dmd_gn_silu_bwd")
     return dx, dma
+
+
+class RewEndLossFn(torch.autograd.Function):
+    """dmd_rew_end_loss under autograd: the kernel leaves d(loss_rew + loss_end) / dlogits beside the losses, the backward scales
+    its reward columns by the gradient that reaches loss_rew and its end columns by the one that reaches loss_end."""
+
+    @staticmethod
+    def forward(ctx, logits: Tensor, rew: Tensor, end: Tensor, mask: Tensor):
+        lg = logits.detach().float().contiguous()
+        r = lg.shape[0]
+        assert lg.shape == (r, 5) and rew.numel() == end.numel() == mask.numel() == r, (lg.shape, rew.shape, end.shape, mask.shape)
+        rw = rew.detach().float().contiguous()
+        en = end.detach().long().contiguous()
+        mk = mask.detach().contiguous()
+        assert mk.element_size() == 1, f"mask of dtype {mk.dtype}: one byte per row (bool or uint8)"
+        losses = torch.empty(2, device=lg.device, dtype=torch.float32)
+        counts = torch.empty(13, device=lg.device, dtype=torch.int64)
+        dlogits = torch.empty_like(lg)
+        nv.check(nv.lib().dmd_rew_end_loss(nv.fptr(lg), nv.fptr(rw), nv.ptr(en), nv.ptr(mk), nv.fptr(losses), nv.fptr(dlogits), nv.ptr(counts),
+                                           r, nv.stream()), "dmd_rew_end_loss")
+        ctx.save_for_backward(dlogits)
+        ctx.mark_non_differentiable(counts)
+        return losses, counts
+
+    @staticmethod
+    def backward(ctx, dlosses: Tensor, _dcounts):
+        (dlogits,) = ctx.saved_tensors
+        d = dlosses.detach().float()
+        return dlogits * torch.stack((d[0], d[0], d[0], d[1], d[1])), None, None, None
+
+
+def rew_end_loss(logits: Tensor, rew: Tensor, end: Tensor, mask: Tensor) -> Tuple[Tensor, Tensor]:
+    """(losses (2,) = [loss_rew, loss_end], counts (13,) int64 = the 3 x 3 reward and the 2 x 2 end confusion matrix) of logits
+    (R, 5) against rew / end (R) over the rows where mask (R; bool or uint8) holds: the masked means of reference
+    rew_end_model.py:72-88 with no gather and no host round trip (an all-false mask gives NaN losses and no gradient, like the
+    mean of an empty selection)."""
+    nv.require_gpu(logits)
+    return RewEndLossFn.apply(logits, rew.reshape(-1), end.reshape(-1), mask.reshape(-1))

@@ -192,6 +192,60 @@ class LstmBurnInFn(torch.autograd.Function):
         return None, dx, None, dw_ih, dw_hh, db, db
 
 
+class LstmSegmentFn(torch.autograd.Function):
+    """nn.LSTM from the zero state over a whole segment, given the input projection of all steps gx = x W_ih^T + b_ih, FRAME-MAJOR
+    (T, B, 4 hd), as ONE autograd node: ys (T, B, hd).  Forward = per step exactly LstmStepFn's launches -- the recurrent GEMM
+    accumulated onto the step's rows of the gate buffer, then the gate kernel, which writes h / c of step i straight into their
+    slices of the output / state buffers: bitwise the T chained LstmStepFn calls.  Backward = BPTT inside the node: per step
+    dmd_lstm_pointwise_bwd and the recurrent data-gradient GEMM (dgx = the dgates buffer: bitwise the chained path's), then
+    ONE dW_hh GEMM and ONE db_hh column sum instead of T of each that autograd adds up with a launch per parameter and step.
+    Summation order of those two: dW_hh[j, k] = sum over the (T - 1) * B rows (step 1 ... T - 1 ascending, sample ascending within
+    a step; step 0 starts from the zero state and contributes nothing) in dmd_linear's order along K; db_hh[j] = torch's column sum
+    over the T * B rows in the same row order.  The chained path sums over B within each step and then over the steps, last first."""
+
+    @staticmethod
+    def forward(ctx, cache: E.PackCache, gx: Tensor, w_hh: Tensor, b_hh: Tensor):
+        t, b, hd = gx.shape[0], gx.shape[1], w_hh.shape[1]
+        gates = gx.detach().float().clone(memory_format=torch.contiguous_format)
+        ys = torch.empty(t, b, hd, device=gx.device, dtype=torch.float32)
+        cs = torch.empty(t + 1, b, hd, device=gx.device, dtype=torch.float32)  # cs[i] = cell state before step i
+        cs[0].zero_()
+        h0 = torch.zeros(b, hd, device=gx.device, dtype=torch.float32)
+        whh, bhh = w_hh.detach(), b_hh.detach()
+        for i in range(t):
+            E.linear(h0 if i == 0 else ys[i - 1], whh, bhh, out=gates[i], accumulate=True)
+            nv.check(nv.lib().dmd_lstm_pointwise(nv.fptr(gates[i]), nv.fptr(cs[i]), nv.fptr(ys[i]), nv.fptr(cs[i + 1]), b, hd, nv.stream()),
+                     "dmd_lstm_pointwise")
+        ctx.save_for_backward(gates, ys, cs)
+        ctx.w_hh_t = cache.get(w_hh, "T", lambda w: w.detach().t().contiguous())
+        return ys
+
+    @staticmethod
+    def backward(ctx, dys: Tensor):
+        gates, ys, cs = ctx.saved_tensors
+        t, b, hd = ys.shape
+        dys = dys.detach().float().contiguous()
+        dgates = torch.empty_like(gates)
+        dh, dc = dys[t - 1], None
+        for i in reversed(range(t)):
+            dc_prev = torch.empty(b, hd, device=dys.device, dtype=torch.float32)
+            nv.check(nv.lib().dmd_lstm_pointwise_bwd(nv.fptr(gates[i]), nv.fptr(cs[i]), nv.fptr(cs[i + 1]), nv.fptr(dh), nv.fptr(dc),
+                                                     nv.fptr(dgates[i]), nv.fptr(dc_prev), b, hd, nv.stream()), "dmd_lstm_pointwise_bwd")
+            dc = dc_prev
+            if i > 0:  # h of step i - 1 feeds ys[i - 1] and step i
+                dh = dys[i - 1] + _mm_nt(dgates[i], ctx.w_hh_t)
+        dg2 = dgates.reshape(t * b, 4 * hd)
+        # (step 0 starts from the zero state: its rows contribute nothing to dW_hh)
+        dw_hh = _mm_nt(dg2[b:].t(), ys[:t - 1].reshape((t - 1) * b, hd).t()) if t > 1 else torch.zeros_like(ctx.w_hh_t.t())
+        return None, dgates, dw_hh, dg2.sum(0)
+
+
+def lstm_segment(cache: E.PackCache, gx: Tensor, lstm) -> Tensor:
+    """ys (T, B, hd) of `lstm` (one layer) stepped from the zero state over gx (T, B, 4 hd), the frame-major input projection."""
+    nv.require_gpu(gx)
+    return LstmSegmentFn.apply(cache, gx, lstm.weight_hh_l0, lstm.bias_hh_l0)
+
+
 def lstm_burn_in(cache: E.PackCache, x: Tensor, tb: int, lstm) -> Tuple[Tensor, Tensor]:
     """(hx, cx) after stepping `lstm` from the zero state over tb frames' features x (tb * k, F), frame-major."""
     nv.require_gpu(x)

@@ -201,15 +201,17 @@ class RewEndModel(nn.Module):
         return logits[:, :, :-2], logits[:, :, -2:], (hx.unsqueeze(0), cx.unsqueeze(0))
 
     # -- training step (reference rew_end_model.py:57-90) ----------------------------------------------------------
-    def logits_with_grad(self, obs: Tensor, act: Tensor, next_obs: Tensor, precision: Optional[str] = None) -> Tensor:
+    def logits_with_grad(self, obs: Tensor, act: Tensor, next_obs: Tensor, precision: Optional[str] = None, segment: bool = False) -> Tensor:
         """predict_rew_end's logits (B, T, 5), from a zero LSTM state, differentiable w.r.t. every parameter.  Encoder:
         the inference kernels under a recorded tape with the hand-written backward (unet_train.EncoderTrainFn);
         LSTM over the segment, the head and the FiLM-table GEMM: lstm_native.LinearFn / LstmStepFn (dmd_linear forward and
-        backward); the action embedding (a gather) is a torch op under autograd."""
+        backward); the action embedding (a gather) is a torch op under autograd.
+        segment: the LSTM as ONE autograd node (lstm_native.LstmSegmentFn: one dW_hh GEMM and one bias sum for the segment) on the
+        features in frame-major order; the same kernels per row, the same logits bit for bit."""
         import torch.nn.functional as F
         from . import unet_train as UT
         from .blocks import AdaGroupNorm
-        from .lstm_native import LinearFn, LstmStepFn
+        from .lstm_native import LinearFn, LstmStepFn, lstm_segment
 
         b, t, c, h, w = obs.shape
         x = torch.cat((obs.reshape(b * t, c, h, w), next_obs.reshape(b * t, c, h, w)), dim=1).detach()
@@ -240,16 +242,64 @@ class RewEndModel(nn.Module):
         w_ih = self.lstm.weight_ih_l0
         s_ = feat.shape[1]
         w_ih_nhwc = w_ih.reshape(4 * hd, e, s_, s_).permute(0, 2, 3, 1).reshape(4 * hd, -1)  # (e h w) -> (h w e) columns
-        gx = LinearFn.apply(self._cache, feat.reshape(b * t, -1), w_ih_nhwc, self.lstm.bias_ih_l0).reshape(b, t, 4 * hd)
-        hx = torch.zeros(b, hd, device=obs.device)
-        cx = torch.zeros(b, hd, device=obs.device)
-        ys = []
-        for i in range(t):
-            hx, cx = LstmStepFn.apply(self._cache, gx[:, i], hx, cx, self.lstm.weight_hh_l0, self.lstm.bias_hh_l0)
-            ys.append(hx)
-        y = torch.stack(ys, dim=1).reshape(b * t, hd)
+        if segment:
+            # frame-major rows (a small copy; a row's summation order in dmd_linear does not depend on its position in the batch)
+            feat_tm = feat.reshape(b, t, -1).transpose(0, 1).reshape(t * b, -1)
+            gx = LinearFn.apply(self._cache, feat_tm, w_ih_nhwc, self.lstm.bias_ih_l0).reshape(t, b, 4 * hd)
+            y = lstm_segment(self._cache, gx, self.lstm).transpose(0, 1).reshape(b * t, hd)
+        else:
+            gx = LinearFn.apply(self._cache, feat.reshape(b * t, -1), w_ih_nhwc, self.lstm.bias_ih_l0).reshape(b, t, 4 * hd)
+            hx = torch.zeros(b, hd, device=obs.device)
+            cx = torch.zeros(b, hd, device=obs.device)
+            ys = []
+            for i in range(t):
+                hx, cx = LstmStepFn.apply(self._cache, gx[:, i], hx, cx, self.lstm.weight_hh_l0, self.lstm.bias_hh_l0)
+                ys.append(hx)
+            y = torch.stack(ys, dim=1).reshape(b * t, hd)
         y = F.silu(LinearFn.apply(self._cache, y, self.head[0].weight, self.head[0].bias))
         return LinearFn.apply(self._cache, y, self.head[2].weight, None).reshape(b, t, -1)
+
+    def put_back_final_observations(self, batch) -> None:
+        """The true final observation put back where an episode of the segment ended (reference rew_end_model.py:65-69), with no
+        host synchronisation: the host only looks at which samples' `info` CARRY a `final_observation` (key presence); whether such
+        a sample really ends inside the segment (`end.any(1)`) and where (`end.argmax(1)`) stays on the device -- its frame is
+        written there, and a sample without an end keeps its frames (a device-side `where`).  Writes through to `batch.obs` like
+        `forward` and the reference, so the frame is also the input of the following step; calling it twice changes nothing."""
+        rows = [i for i, info in enumerate(getattr(batch, "info", None) or ()) if "final_observation" in info]
+        if not rows:
+            return
+        dev = batch.obs.device
+        nv.check_current_device(dev)
+        final = torch.stack([batch.info[i]["final_observation"] for i in rows]).to(dev, non_blocking=True)
+        idx = torch.tensor(rows, dtype=torch.long).to(dev, non_blocking=True)
+        end = batch.end[:, :-1][idx]  # (k, t)
+        pos = end.argmax(dim=1)
+        next_obs = batch.obs[:, 1:]
+        keep = next_obs[idx, pos]
+        next_obs[idx, pos] = torch.where(end.bool().any(dim=1).reshape(-1, 1, 1, 1), final.to(keep.dtype), keep)
+
+    def forward_static(self, batch):
+        """`forward` with no host synchronisation and no data-dependent shape, so that the training step records into a hipGraph
+        (train_graph.graphed_rew_end_step): assumes `put_back_final_observations(batch)` has run; the LSTM over the segment is one
+        autograd node (logits_with_grad(segment=True): the same logits bit for bit); the masked cross-entropies, their gradient
+        and both confusion matrices are one launch (grad_ops.rew_end_loss) instead of boolean gathers and torch.bincount.  Returns
+        (loss, metrics) with `forward`'s keys and dtypes.  A batch that is all padding gives a NaN loss and no gradient."""
+        from . import grad_ops as G
+
+        nv.check_current_device(batch.obs.device)
+        logits = self.logits_with_grad(batch.obs[:, :-1], batch.act[:, :-1], batch.obs[:, 1:], segment=True)
+        b, t = logits.shape[:2]
+        losses, counts = G.rew_end_loss(logits.reshape(b * t, 5), batch.rew[:, :-1].contiguous(), batch.end[:, :-1].contiguous(),
+                                        batch.mask_padding[:, :-1].contiguous())
+        loss_rew, loss_end = losses[0], losses[1]
+        loss = loss_rew + loss_end
+        metrics = {
+            "loss_rew": loss_rew.detach(),
+            "loss_end": loss_end.detach(),
+            "loss_total": loss.detach(),
+            "confusion_matrix": {"rew": counts[:9].reshape(3, 3), "end": counts[9:].reshape(2, 2)},
+        }
+        return loss, metrics
 
     def forward(self, batch):
         """Cross-entropy losses of the reward (sign-clipped, 3 classes) and termination (2 classes) heads over the

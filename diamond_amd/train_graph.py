@@ -25,6 +25,11 @@ on parameter versions / that hook: the warm-up steps' optimizer updates make eve
 too: the step ends with an explicit refresh of every cache behind the optimizer update (one dmd_pack_jobs launch per cache,
 in place), so after a replay the packed copies equal the parameters -- also for readers that never look a copy up again (the
 sampler's captured imagination graphs read the packed buffers directly).
+
+The reward / end model (the trainer's second world-model component) records the same way through `graphed_rew_end_step`: its
+`forward` asks the host which episodes ended and gathers by a boolean mask, so the captured step is `forward_static`, and the
+one thing that needs the host -- which samples carry a `final_observation` -- runs on every incoming batch before it is copied
+into the static buffers (`stage`).
 """
 from __future__ import annotations
 
@@ -60,12 +65,20 @@ def _refresh_weight_caches(model: nn.Module) -> None:
 
 class GraphedTrainStep:
     def __init__(self, model: nn.Module, optimizer: torch.optim.Optimizer, max_grad_norm: Optional[float], example_batch: Any,
-                 warmup_steps: int = 3, fields: Tuple[str, ...] = ("obs", "act", "mask_padding")) -> None:
+                 warmup_steps: int = 3, fields: Tuple[str, ...] = ("obs", "act", "mask_padding"),
+                 step_fn: Optional[Callable[[Any], Tuple[Tensor, Dict[str, Any]]]] = None,
+                 stage: Optional[Callable[[Any], None]] = None) -> None:
+        """step_fn: (static_batch) -> (loss, metrics), what the captured step calls instead of `model` (it must be free of host
+        synchronisations and data-dependent shapes).  stage: (batch) -> None, run on the example batch and on every incoming
+        batch BEFORE it is copied into the static buffers -- eager, outside the graph: the place for what needs the host."""
         assert torch.cuda.is_available(), "GraphedTrainStep needs the GPU"
         for group in optimizer.param_groups:
             assert group.get("capturable", False), \
                 "construct the optimizer with capturable=True (its step counter must live on the device to be replayed)"
         self.model, self.optimizer, self.max_grad_norm, self.fields = model, optimizer, max_grad_norm, fields
+        self.step_fn, self.stage = (model if step_fn is None else step_fn), stage
+        if stage is not None:
+            stage(example_batch)
         self.static = {k: getattr(example_batch, k).detach().clone() for k in fields}
         self._batch = type("StaticBatch", (), {})()
         for k, v in self.static.items():
@@ -91,7 +104,7 @@ class GraphedTrainStep:
         # (gradients stay allocated: the captured backward writes, not accumulates, into them at every replay)
 
     def _eager(self, zero: bool = True):
-        loss, metrics = self.model(self._batch)
+        loss, metrics = self.step_fn(self._batch)
         loss.backward()
         if self.max_grad_norm is not None:
             torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_grad_norm)
@@ -102,6 +115,8 @@ class GraphedTrainStep:
         return loss.detach(), {k: (v.detach() if isinstance(v, Tensor) else v) for k, v in metrics.items()}
 
     def __call__(self, batch: Any) -> Tuple[Tensor, Dict[str, Any]]:
+        if self.stage is not None:
+            self.stage(batch)
         for k, buf in self.static.items():
             src = getattr(batch, k)
             assert src.shape == buf.shape and src.dtype == buf.dtype, \
@@ -118,3 +133,21 @@ class GraphedTrainStep:
         # graphs captured elsewhere from the same weights (DiffusionSampler.sample_ring_graphed) read the new values through
         # the same pointers.
         return self.loss, self.metrics
+
+
+def graphed_rew_end_step(model: nn.Module, optimizer: torch.optim.Optimizer, max_grad_norm: Optional[float], example_batch: Any,
+                         warmup_steps: int = 3) -> GraphedTrainStep:
+    """The reward / end model's training step (reference trainer.py:349-388 on `agent.rew_end_model`) as one replayed hipGraph:
+
+        step = graphed_rew_end_step(agent.rew_end_model, opt, max_grad_norm, example_batch)    # opt: capturable=True
+        for batch in loader:
+            loss, metrics = step(batch)
+
+    Per batch, eagerly: RewEndModel.put_back_final_observations (writes through to `batch.obs`, like `forward`), then the copy of
+    obs / act / rew / end / mask_padding into the static buffers; replayed: RewEndModel.forward_static, backward, clipping, the
+    optimizer update and the refresh of the packed weights.  The returned loss and metrics -- the nested confusion matrices
+    included, returned as they are -- are the graph's own buffers: the next replay overwrites them, so clone what has to outlive
+    the step (as for the denoiser)."""
+    return GraphedTrainStep(model, optimizer, max_grad_norm, example_batch, warmup_steps=warmup_steps,
+                            fields=("obs", "act", "rew", "end", "mask_padding"), stage=model.put_back_final_observations,
+                            step_fn=model.forward_static)

@@ -378,6 +378,19 @@ int dmd_lstm_pointwise_bwd(const float* gates, const float* c_prev, const float*
  * (env_loop.py:32, world_model_env.py:103-104). */
 int dmd_categorical_sample(const float* logits, const float* expo, int64_t* out, int N, int A, dmd_stream_t stream);
 
+/* (ABI v11 addition) The reward / end training loss (rew_end_model.py:72-88) in ONE launch of one workgroup, with nothing
+ * data-dependent on the host (capturable).  logits (R, 5) fp32 contiguous: columns 0-2 the reward head, 3-4 the end head; rew (R)
+ * fp32; end (R) int64; mask (R) one byte per row (0 = padding).  With n = the number of masked rows:
+ *   losses[0]  mean over the masked rows of the cross-entropy of logits[:, 0:3] against class sign(rew) + 1 (-0.0, 0.0: class 1)
+ *   losses[1]  the same of logits[:, 3:5] against class (end != 0)
+ *   dlogits    (R, 5): gradient of losses[0] + losses[1], (softmax - onehot) / n per head; exact zeros on unmasked rows
+ *   counts     int64 [13]: the confusion matrices [true][argmax] of the masked rows, 3 x 3 then 2 x 2, row-major; argmax ties go
+ *              to the lowest index
+ * n == 0: both losses NaN (the mean of an empty selection), dlogits and counts all zero.  fp32 log-soft-max with the row maximum
+ * subtracted; fp64 loss sums and integer counts in a fixed order (no atomics): bitwise reproducible.  1 <= R <= 2^20. */
+int dmd_rew_end_loss(const float* logits, const float* rew, const int64_t* end, const uint8_t* mask, float* losses, float* dlogits,
+                     int64_t* counts, int R, dmd_stream_t stream);
+
 /* ---- actor-critic encoder backward (what ATen autograd does for actor_critic.py:101-113 /
  *      blocks.py:116-123 under loss.backward(), trainer.py:366) ------------------------------ */
 
