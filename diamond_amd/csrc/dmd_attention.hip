@@ -1,7 +1,12 @@
-// dmd_attention -- softmax(q k^T / sqrt(d)) v for SelfAttention2d (models/blocks.py:62-72),
-// flash-style: K/V tiles staged in LDS, online softmax, QK^T and PV on
-// v_mfma_f32_16x16x4_f32 (head_dim d = 8, ATTN_HEAD_DIM blocks.py:14).
+// dmd_attention -- softmax(q k^T / sqrt(d)) v for SelfAttention2d (models/blocks.py:62-72), head_dim d = 8 (ATTN_HEAD_DIM
+// blocks.py:14), K / V tiles of 256 keys staged in LDS.  Two kernels, chosen by T alone (precision contract: include/diamond_hip.h):
+//   T % 256 != 0, and every dmd_attention_valid: attention_kernel below -- exact fp32, flash-style ONLINE softmax, QK^T and PV on
+//                 v_mfma_f32_16x16x4_f32;
+//   T % 256 == 0 (256 = the default denoiser's 16x16 level, training forward included; 1024 / 4096 at 256x256):
+//                 attention_f16x2_kernel further down -- split-fp16 operands on v_mfma_f32_16x16x32_f16, TWO passes over the
+//                 keys, no online rescale.
 //
+// attention_kernel:
 // Layout trick: compute the TRANSPOSED score block S^T[key][query] = K Q^T so that a lane
 // (j = lane & 15, kg = lane >> 4) owns 4 keys {4 kg + r} of ONE query j:
 //   * the softmax statistics of query j live in the 4 lanes {j, j+16, j+32, j+48}
@@ -104,9 +109,11 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
-// attention_f16x2_kernel -- the same attention for long sequences (T a multiple of 256: 1024 / 4096 tokens at the 32x32 /
-// 64x64 levels of the 256x256 configuration) on the f16 matrix cores with SPLIT fp32 operands (x = h + l, fp16 pieces,
-// as in dmd_conv_f16ws.hip).  With head_dim 8 a (query, key) pair costs 16 MACs and one exponential: the kernel is bound by
+// attention_f16x2_kernel -- the same attention for T a multiple of 256 (256 tokens at the default denoiser's 16x16 level, in
+// sampling and in the training step's forward; 1024 / 4096 tokens at the 32x32 / 64x64 levels of the 256x256 configuration) on the
+// f16 matrix cores with SPLIT fp32 operands (x = h + l, fp16 pieces, as in dmd_conv_f16ws.hip: each operand off by at most
+// max(2^-22 |x|, 2^-25), usable up to the end of fp16, nothing clamped -- a finite operand whose h piece overflows makes the
+// outputs it feeds NaN; NaN / +-Inf operands behave as in fp32, af_split8).  With head_dim 8 a (query, key) pair costs 16 MACs and one exponential: the kernel is bound by
 // the vector unit's issue port (v_exp_f32 takes two of its slots: 8 cycles per wave64 instruction, additive with plain VALU work,
 // tools/probe/trans_probe.hip / profiles/r04_trans_probe.txt), so everything else is taken off it:
 //   * TWO passes over the keys instead of an online softmax.  Pass 1: S^T = K Q^T blocks and a running per-lane maximum
@@ -161,12 +168,18 @@ struct AfTile {
   _Float16 vt[16][AF_VS];  // rows 0..7: v_h[dim][key], rows 8..15: v_l[dim][key]
 };
 
+// INF_IN_L (the keys): an infinite element is held as h = 0, l = +-Inf instead of h = +-Inf, l = Inf - Inf = NaN.  The score's
+// slots are then q_h * 0 + q_h * (+-Inf) + q_l * 0 (+ 0 * 0 in the unused group) = sign(q) * Inf, fp32's q * k: a key whose score is
+// -Inf drops out of its row, one whose score is +Inf makes the row NaN, and q = 0 against it is NaN, as in fp32.  With h = +-Inf
+// the q_l * k_h slot (q_l takes either sign) and the unused group's k_h * 0 made every score of that key NaN.  A FINITE element
+// beyond fp16 still splits into h = +-Inf, l = -+Inf: NaN, nothing is clamped.
+template <bool INF_IN_L = false>
 __device__ __forceinline__ void af_split8(const f32x4& a, const f32x4& b, att_h8& h, att_h8& l) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    h[e] = (_Float16)a[e];
+    h[e] = (INF_IN_L && __builtin_isinf(a[e])) ? (_Float16)0.f : (_Float16)a[e];
     l[e] = (_Float16)(a[e] - (float)h[e]);
-    h[4 + e] = (_Float16)b[e];
+    h[4 + e] = (INF_IN_L && __builtin_isinf(b[e])) ? (_Float16)0.f : (_Float16)b[e];
     l[4 + e] = (_Float16)(b[e] - (float)h[4 + e]);
   }
 }
@@ -182,16 +195,40 @@ __global__ __launch_bounds__(256, 2) void attention_f16x2_kernel(const float* __
   const float* base = qkv + (size_t)n * T * row;
   const int ntiles = T / AF_KT;
 
-  // Q operand of S^T = K Q^T, per 16-query group: k-slots {q_h | q_h | q_l | 0}, scaled by log2(e) / sqrt(d)
-  att_h8 bq[AF_QG];
+  // Q operand of S^T = K Q^T, per 16-query group: k-slots {q_h | q_h | q_l | 0}, scaled by log2(e) / sqrt(d).
+  // REBALANCING: the fp16 pieces carry 2^-22 of an operand only from 2^-3 upwards (below, their absolute floor 2^-25).  When every
+  // q' of the workgroup's 256 queries is below 2^-3 -- tiny queries against keys near the end of fp16 -- q' is multiplied by the
+  // power of two that brings the largest into [1, 2) and the workgroup's copy of K (split while staging) by its inverse, < 2^-3:
+  // the scores are the same numbers, the keys cannot overflow.  Otherwise the factor is 1 and every bit is as without it.
+  f32x4 qa[AF_QG], qb[AF_QG];
+  float qmax = 0.f;
 #pragma unroll
   for (int g = 0; g < AF_QG; ++g) {
     const float* qp = base + (size_t)(q0 + g * 16 + j) * row + h * 8;
-    f32x4 a = *(const f32x4*)qp, b = *(const f32x4*)(qp + 4);
-    a *= qscale;
-    b *= qscale;
+    qa[g] = *(const f32x4*)qp;
+    qb[g] = *(const f32x4*)(qp + 4);
+    qa[g] *= qscale;
+    qb[g] *= qscale;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) qmax = fmaxf(qmax, fmaxf(fabsf(qa[g][e]), fabsf(qb[g][e])));
+  }
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) qmax = fmaxf(qmax, __shfl_xor(qmax, o, 64));
+  float* red = (float*)&tiles[1];  // free until pass 1 stages its second tile, behind the next barrier
+  if (lane == 0) red[wave] = qmax;
+  __syncthreads();
+  qmax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float kscale = 1.f, qs = 1.f;
+  if (qmax < 0.125f && qmax > 1e-30f) {
+    const unsigned pw = __builtin_bit_cast(unsigned, qmax) & 0x7f800000u;  // 2^floor(log2 qmax)
+    kscale = __builtin_bit_cast(float, pw);
+    qs = __builtin_bit_cast(float, 0x7f000000u - pw);
+  }
+  att_h8 bq[AF_QG];
+#pragma unroll
+  for (int g = 0; g < AF_QG; ++g) {
     att_h8 qh, ql;
-    af_split8(a, b, qh, ql);
+    af_split8(qa[g] * qs, qb[g] * qs, qh, ql);
     att_h8 z;
 #pragma unroll
     for (int e = 0; e < 8; ++e) z[e] = (_Float16)0.f;
@@ -211,7 +248,7 @@ __global__ __launch_bounds__(256, 2) void attention_f16x2_kernel(const float* __
   };
   auto stage_store = [&](AfTile& tl, bool with_v) {
     att_h8 hh, ll;
-    af_split8(sk0, sk1, hh, ll);
+    af_split8<true>(sk0 * kscale, sk1 * kscale, hh, ll);
     tl.kh[tid] = hh;
     tl.kl[tid] = ll;
     if (with_v) {
@@ -337,7 +374,7 @@ extern "C" int dmd_attention(const float* qkv, float* out, int N, int T, int C, 
   DMD_CHECK_ARG(head_dim == 8, "attention: head_dim must be 8 (ATTN_HEAD_DIM), got %d", head_dim);
   DMD_CHECK_ARG(C % 8 == 0 && T % 64 == 0 && N > 0, "attention: need C %% 8 == 0, T %% 64 == 0 (T=%d C=%d)", T, C);
   if (T % 256 == 0) {
-    // long sequences (1024 / 4096 tokens of the 256x256 configuration): split-fp16 two-pass kernel
+    // whole 256-key tiles (256 tokens of the default 16x16 level, 1024 / 4096 of the 256x256 configuration): split-fp16 two-pass kernel
     hipLaunchKernelGGL(attention_f16x2_kernel, dim3(T / 256, C / 8, N), dim3(256), 0, (hipStream_t)stream, qkv, out, T, C,
                        1.4426950408889634f / sqrtf((float)head_dim));
     DMD_LAUNCH_CHECK();

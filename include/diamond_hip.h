@@ -181,9 +181,35 @@ typedef struct dmd_linear_params {
 } dmd_linear_params;
 int dmd_linear(const dmd_linear_params* p, dmd_stream_t stream);
 
-/* dmd_attention: softmax(q k^T / sqrt(d)) v per (image, head) over T tokens, streaming
- * K/V tiles through LDS with an online softmax.  qkv is NHWC (N, T, 3C): q | k | v channel
- * thirds, head h = channels [h*d, (h+1)*d) of each third (blocks.py:66-71).  d == 8. */
+/* dmd_attention: softmax(q k^T / sqrt(d)) v per (image, head) over T tokens (T % 64 == 0), K / V tiles of 256 keys staged in
+ * LDS.  qkv is NHWC (N, T, 3C): q | k | v channel thirds, head h = channels [h*d, (h+1)*d) of each third (blocks.py:66-71).
+ * d == 8.  Which kernel runs depends on T alone:
+ *   T % 256 != 0 (64, 192, 320 ...: the 8x8 level)   attention_kernel: fp32 operands on the fp32 MFMAs, online softmax (running
+ *       maximum, rescale per 16-key block).  IEEE fp32 throughout: full fp32 range, no floor; NaN / +-Inf operands give what an
+ *       fp32 evaluation of the formula gives.
+ *   T % 256 == 0 (256 = the default denoiser's 16x16 level, 1024 / 4096 = the 256x256 configuration)   attention_f16x2_kernel:
+ *       SPLIT-fp16 operands on the f16 MFMAs in TWO passes over the keys (row maxima, then weights / sums / PV).  The forward of
+ *       the TRAINING step takes it too: there is no precision switch for attention (DIAMOND_CONV_PRECISION=f32 does not reach
+ *       it), so dmd_attention_bwd differentiates around a split-fp16 y.  dmd_attention_valid never takes it.
+ * PRECISION CONTRACT of the two-pass kernel (tests/test_attention_precision.py walks its edges; measured table in
+ * profiles/attention_precision.txt):
+ *   * operands: k, v and q' = q * log2(e) / sqrt(d) are each held as two fp16 pieces x = h + l: off by at most
+ *     max(2^-22 |x|, 2^-25).  The relative part applies from |x| >= 2^-3 on; below, the ABSOLUTE floor 2^-25 does.  Scores keep the
+ *     three products q'_h k_h + q'_h k_l + q'_l k_h in fp32: their error is about 2^-22 sum_i |q'_i k_i| (it scales with the
+ *     products' magnitudes, not with the score differences), plus 2^-25 sum_i |k_i| once q' is below 2^-3 and 2^-25 sum_i |q'_i|
+ *     once k is.  When EVERY q' of a workgroup's 256 queries is below 2^-3, the kernel multiplies them by the power of two that
+ *     brings the largest into [1, 2) and its copy of the keys by the inverse (exact; the factor is 1 otherwise and no bit
+ *     changes), so tiny queries against keys near 65504 keep the relative error.  Within about 4x of an fp32 evaluation of the
+ *     formula on every input family of the test file.  v far below 2^-3 is NOT rebalanced: outputs are off by up to 2^-24
+ *     absolute whatever their size (scale v up by a power of two first).
+ *   * range: up to the end of fp16 (65504) for k, v and q'.  NOTHING IS CLAMPED: a finite operand beyond it is LOUD and
+ *     CONFINED: the split gives h = +-Inf, l = -+Inf, so a k element makes every output of its (image, head) NaN, a q element
+ *     every output of its query row, a v element every output of its dim in its (image, head); every other output keeps its
+ *     bits.  Never finite and wrong.  NaN and +-Inf operands give the non-finite pattern of an fp32 evaluation: an infinite k
+ *     element is held as h = 0, l = +-Inf, so its key drops out of the rows whose score against it is -Inf and makes the rows
+ *     NaN whose score is +Inf (or 0 * Inf).
+ *   * weights: p = 2^(s - max + 13) as two fp16 pieces, divided by their fp32 sum: a weight below 2^-38 of its row's largest is
+ *     dropped (pieces stop at 2^-25 of 2^13), each weight is off by at most 2^-22 of itself or 2^-38 of the largest. */
 int dmd_attention(const float* qkv, float* out, int N, int T, int C, int head_dim, dmd_stream_t stream);
 /* ... over an (H, W) token grid of which only (valid_h, valid_w) exists (see dmd_conv_params: VALID EXTENT): keys outside it
  * do not take part in the softmax; outputs of queries outside it are unspecified */

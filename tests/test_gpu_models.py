@@ -750,6 +750,51 @@ def test_lowres_chain_matches_launch_by_launch(attn_depths, b):
     assert err < 1e-5, err
 
 
+def test_lowres_chain_attention_with_large_scores_vs_float64_oracle():
+    """lowres_chain_kernel's own attention (exp2f of fp32 scores) away from random-weight scores: the q and k rows of every
+    attention block's qkv_proj weight times 6 (scores x 36), attn_depths (0, 0, 0, 1).  The fused launch and the launch-by-launch
+    path are both compared with the oracle's inner_model in float64 on the same weights: the chain's error is at most twice the
+    launch-by-launch path's, or 1e-5 of the output scale if that is larger."""
+    from diamond_amd import blocks as BL
+    from diamond_amd import engine as E
+    from diamond_amd.testing import synthetic_actions, synthetic_frames
+    from oracle import diamond_oracle as O
+
+    attn_depths, b = (0, 0, 0, 1), 2
+    ag = make_agent(attn_depths)
+    scaled = 0
+    with torch.no_grad():
+        for m in ag.denoiser.modules():
+            if hasattr(m, "qkv_proj"):
+                c = m.qkv_proj.weight.shape[0] // 3
+                m.qkv_proj.weight[:2 * c].mul_(6.0)
+                scaled += 1
+    assert scaled == 7  # two mid blocks + the level's own two down and three up blocks
+    g = torch.Generator().manual_seed(17 + b)
+    obs = synthetic_frames(g, b, 12, 64, 64)
+    act = synthetic_actions(g, 4, b, 4)
+    x = torch.randn(b, 3, 64, 64, generator=g)
+    sigma = torch.tensor([5.0, 0.3])
+    spec = O.DenoiserSpec(attn_depths=attn_depths)
+    sd = {k: v.detach().double().cpu() for k, v in ag.denoiser.state_dict().items()}
+    c_in, _, _, c_noise = O.conditioners(spec, sigma.double())
+    ref = O.inner_model(sd, spec, x.double() * c_in, c_noise, obs.double() / spec.sigma_data, act)
+    errs = {}
+    try:
+        for mode in (True, False):
+            BL.LOWRES_CHAIN = 3 if mode else 0
+            nv.PROFILER = E.LaunchProfiler()
+            out = ag.denoiser.compute_model_output(x.to(DEV), obs.to(DEV), act.to(DEV), sigma.to(DEV))
+            keys = nv.PROFILER.summary()
+            assert ("lowres_chain_kernel" in keys) == mode, keys.keys()
+            errs[mode] = rel_err(out, ref)
+    finally:
+        BL.LOWRES_CHAIN = 3
+        nv.PROFILER = None
+    print(f"lowres chain, q / k weights x 6, vs float64 oracle: chain {errs[True]:.3e}, launch by launch {errs[False]:.3e}")
+    assert errs[True] <= max(2 * errs[False], 1e-5), errs
+
+
 def test_rew_end_lowres_chain_matches_launch_by_launch(agent):
     """dmd_lowres_chain32 (the 8x8 x 32-channel tail of the reward / end encoder: last level + the final attention group in
     one launch) against the launch-by-launch path: logits and LSTM state within 1e-5, burn-in (T = 3) and step form."""
