@@ -406,8 +406,10 @@ extern "C" int dmd_attention_valid(const float* qkv, float* out, int N, int H, i
 //   P = softmax(q k^T / sqrt(d)),  y = P v.   Given dy:
 //   D_i = dy_i . y_i ;  dP_ij = dy_i . v_j ;  dS_ij = P_ij (dP_ij - D_i)
 //   dq_i = sum_j dS_ij k_j / sqrt(d) ;  dk_j = sum_i dS_ij q_i / sqrt(d) ;  dv_j = sum_i P_ij dy_i
-// Two kernels, fp32 VALU (the default model attends over 64 tokens at the 8x8 level only: 3 MFLOP per image;
-// this path is launch-bound, not FLOP-bound):
+// Two kernels, fp32 VALU, one thread per query (key) sweeping all T keys (queries) serially: the SMALL-T path (64 tokens at the 8x8
+// level, 256 at the default denoiser's 16x16 level, valid extents off the tile grid), where a step is bound by its launches rather
+// than by these FLOPs.  Long token grids (1024 / 4096 tokens of the 256x256 configuration) take dmd_attention_bwd_mfma at the end
+// of this file; unet_train.py chooses by the valid token count (ATTN_BWD_MFMA_MIN_T).
 //   rows kernel: one thread per query row i -- softmax statistics (m_i, l_i) by a first sweep over the keys, then dq_i;
 //                writes (m_i, l_i, D_i) for the second kernel;
 //   cols kernel: one thread per key row j -- dk_j, dv_j by a sweep over the queries.
@@ -651,6 +653,303 @@ extern "C" int dmd_attention_bwd_valid(const float* qkv, const float* y, const f
                      valid_h, valid_w, C, nbv);
   hipLaunchKernelGGL(attention_bwd_valid_cols_kernel, dim3(nbv, C / 8, N), dim3(64), 0, st, qkv, dy, (const float*)workspace, dqkv, T,
                      W, valid_h, valid_w, C);
+  DMD_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// dmd_attention_bwd_mfma -- the same gradient (formulae above attention_bwd_rows_kernel) for LONG token grids, on
+// v_mfma_f32_16x16x4_f32 with exact fp32 operands (dy has no bounded range: no split-fp16 here).  The structure mirrors the scalar
+// pair -- a query-side kernel that owns dq and the row statistics, a key-side kernel that owns dk and dv -- so there are no
+// atomics and every sum has a fixed order.  Tokens are addressed by their VALID index li <-> token (li / vw) * W + li % vw of an
+// (H, W) grid (dmd_attention_bwd_valid's convention; the full grid is H = 1, W = T): nothing outside the extent is read, and the
+// whole-grid call walks the tokens exactly as the (1, T, 1, T) call does.
+//   attention_bwd_mfma_q_kernel: 4 waves x 16 queries; K / V tiles of 256 keys double-buffered in LDS.  attention_kernel's
+//     layout trick: S^T[key][query] = K Q^T and dP^T = V dY^T leave lane (j = lane & 15, kg = lane >> 4) with keys {4 kg + r} of
+//     ONE query j, so m, D and 1 / l are per-lane scalars and the four p~ (dP - D) are directly the B operand of
+//     dq^T[dim][query] += K^T dS~^T.  TWO passes over the keys: the first finds the row maximum m of the raw dot products q . k,
+//     the second forms p~ = 2^((q . k - m) log2(e) / sqrt(d)) (one subtraction, one multiplication, one v_exp_f32 per pair; exactly
+//     softmax's x - max(x)), the row sum l and dq~; dq = dq~ / l / sqrt(d).  Keys behind the last valid one get the score -inf
+//     (their LDS rows are zero).  Writes (m, l, D, 0) per valid query into the workspace.  Its workgroups behind the valid ones
+//     write the dqkv rows outside the extent as zero.
+//   attention_bwd_mfma_k_kernel: 4 waves x 16 keys, k and v of the lane's key in registers; tiles of 128 queries (q, dy, both
+//     also transposed, and (m, 1 / l, D)) double-buffered in LDS.  S[query][key] and dP = dY V^T have the key in the lane's column;
+//     dk^T[dim][key] += Q^T dS, dv^T[dim][key] += dY^T P.  Query rows behind the last valid one are zero with 1 / l = 0.
+// Lanes of a partial last block compute on the last valid token and write nothing.
+// ------------------------------------------------------------------------------------------------
+#define AB_KT 256                 // keys per LDS tile of the query-side kernel
+#define AB_QT 128                 // queries per LDS tile of the key-side kernel
+#define AB_PAD 16                 // row padding of the transposed copies
+#define AB_EXP_SCALE 0.51006973f  // log2(e) / sqrt(8)
+#define AB_SCALE 0.35355339059327373f
+
+__device__ __forceinline__ int ab_token(int li, int W, int vw) {
+  const int r = li / vw;
+  return r * W + (li - r * vw);
+}
+
+struct AbKeyTile {
+  float k[AB_KT][8];
+  float v[AB_KT][8];
+  float kt[8][AB_KT + AB_PAD];  // K^T[dim][key]
+};
+
+struct AbQueryTile {
+  float q[AB_QT][8];
+  float dy[AB_QT][8];
+  float qt[8][AB_QT + AB_PAD];   // Q^T[dim][query]
+  float dyt[8][AB_QT + AB_PAD];  // dY^T[dim][query]
+  f32x4 st[AB_QT];               // m, 1 / l, D, 0
+};
+
+__global__ __launch_bounds__(256) void attention_bwd_mfma_q_kernel(const float* __restrict__ qkv, const float* __restrict__ y,
+                                                                   const float* __restrict__ dy, float* __restrict__ dqkv,
+                                                                   float* __restrict__ rowstat, int T, int W, int vh, int vw, int C,
+                                                                   int nbv) {
+  __shared__ AbKeyTile tiles[2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = lane & 15, kg = lane >> 4;
+  const int n = blockIdx.z, h = blockIdx.y, NH = C / 8, V = vh * vw;
+  const size_t row = (size_t)3 * C;
+  const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
+  if ((int)blockIdx.x >= nbv) {
+    // the m-th token outside the extent: rows < vh, columns >= vw first, then the rows >= vh
+    const int m = ((int)blockIdx.x - nbv) * 256 + tid, side = vh * (W - vw);
+    if (m >= T - V) return;
+    int r, c;
+    if (m < side) {
+      r = m / (W - vw);
+      c = vw + (m - r * (W - vw));
+    } else {
+      r = vh + (m - side) / W;
+      c = (m - side) - (r - vh) * W;
+    }
+    float* o = dqkv + ((size_t)n * T + (size_t)r * W + c) * row + h * 8;
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      *(f32x4*)(o + t * C) = zero4;
+      *(f32x4*)(o + t * C + 4) = zero4;
+    }
+    return;
+  }
+  const float* base = qkv + (size_t)n * T * row;
+  const int lq = blockIdx.x * 64 + wave * 16 + j;
+  const size_t qtok = (size_t)n * T + ab_token(lq < V ? lq : V - 1, W, vw);
+  // B operands of S^T = K Q^T and dP^T = V dY^T: lane (query j, k' = kg), step s uses dim 2 kg + s
+  const float* qp = qkv + qtok * row + h * 8 + 2 * kg;
+  const float* dyp = dy + qtok * C + h * 8 + 2 * kg;
+  const float* yp = y + qtok * C + h * 8 + 2 * kg;
+  const float qa = qp[0], qb = qp[1], da = dyp[0], db = dyp[1];
+  float D = __builtin_fmaf(db, yp[1], da * yp[0]);
+  D += __shfl_xor(D, 16, 64);
+  D += __shfl_xor(D, 32, 64);
+
+  const int ntiles = (V + AB_KT - 1) / AB_KT;
+  f32x4 sk0, sk1, sv0, sv1;
+  auto stage_load = [&](int t, bool with_v) {
+    const int lk = t * AB_KT + tid;
+    sk0 = sk1 = sv0 = sv1 = zero4;
+    if (lk < V) {
+      const float* kp = base + (size_t)ab_token(lk, W, vw) * row + C + h * 8;
+      sk0 = *(const f32x4*)kp;
+      sk1 = *(const f32x4*)(kp + 4);
+      if (with_v) {
+        sv0 = *(const f32x4*)(kp + C);
+        sv1 = *(const f32x4*)(kp + C + 4);
+      }
+    }
+  };
+  auto stage_store = [&](AbKeyTile& tl, bool with_v) {
+    *(f32x4*)&tl.k[tid][0] = sk0;
+    *(f32x4*)&tl.k[tid][4] = sk1;
+    if (with_v) {
+      *(f32x4*)&tl.v[tid][0] = sv0;
+      *(f32x4*)&tl.v[tid][4] = sv1;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        tl.kt[e][tid] = sk0[e];
+        tl.kt[4 + e][tid] = sk1[e];
+      }
+    }
+  };
+  // S^T block of 16 keys from k0: s[r] = q_j . k_{k0 + 4 kg + r}, -inf behind the tile's nk keys
+  auto scores = [&](const AbKeyTile& tl, int k0, int nk) -> f32x4 {
+    f32x4 s = __builtin_amdgcn_mfma_f32_16x16x4f32(tl.k[k0 + j][2 * kg], qa, zero4, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_16x16x4f32(tl.k[k0 + j][2 * kg + 1], qb, s, 0, 0, 0);
+    if (k0 + 16 > nk) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (k0 + 4 * kg + r >= nk) s[r] = -INFINITY;
+    }
+    return s;
+  };
+
+  // ---------------- pass 1: row maxima of q . k ----------------
+  float m = -INFINITY;
+  stage_load(0, false);
+  stage_store(tiles[0], false);
+  __syncthreads();
+  for (int t = 0; t < ntiles; ++t) {
+    const AbKeyTile& tl = tiles[t & 1];
+    if (t + 1 < ntiles) stage_load(t + 1, false);
+    const int nk = (V - t * AB_KT) < AB_KT ? (V - t * AB_KT) : AB_KT;
+    for (int k0 = 0; k0 < nk; k0 += 16) {
+      const f32x4 s = scores(tl, k0, nk);
+      m = fmaxf(fmaxf(fmaxf(m, s[0]), fmaxf(s[1], s[2])), s[3]);
+    }
+    if (t + 1 < ntiles) stage_store(tiles[(t + 1) & 1], false);
+    __syncthreads();
+  }
+  m = fmaxf(m, __shfl_xor(m, 16, 64));
+  m = fmaxf(m, __shfl_xor(m, 32, 64));
+
+  // ---------------- pass 2: weights, row sum, dq~^T[dim][query] += K^T dS~^T ----------------
+  f32x4 acc = zero4;  // dq~^T[dd = 4 kg + r][query j]  (kg >= 2: padding rows)
+  float l = 0.f;
+  stage_load(0, true);
+  stage_store(tiles[0], true);
+  __syncthreads();
+  for (int t = 0; t < ntiles; ++t) {
+    const AbKeyTile& tl = tiles[t & 1];
+    if (t + 1 < ntiles) stage_load(t + 1, true);
+    const int nk = (V - t * AB_KT) < AB_KT ? (V - t * AB_KT) : AB_KT;
+    for (int k0 = 0; k0 < nk; k0 += 16) {
+      const f32x4 s = scores(tl, k0, nk);
+      f32x4 dp = __builtin_amdgcn_mfma_f32_16x16x4f32(tl.v[k0 + j][2 * kg], da, zero4, 0, 0, 0);
+      dp = __builtin_amdgcn_mfma_f32_16x16x4f32(tl.v[k0 + j][2 * kg + 1], db, dp, 0, 0, 0);
+      f32x4 p, ds;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        p[r] = __builtin_amdgcn_exp2f((s[r] - m) * AB_EXP_SCALE);
+        ds[r] = p[r] * (dp[r] - D);
+      }
+      l += (p[0] + p[1]) + (p[2] + p[3]);
+      // A = K^T[dd i = lane & 15][key 4 kg + t], B = dS~^T[key][query j] = ds[t]
+      f32x4 kf = zero4;
+      if (j < 8) kf = *(const f32x4*)&tl.kt[j][k0 + 4 * kg];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[u], ds[u], acc, 0, 0, 0);
+    }
+    if (t + 1 < ntiles) stage_store(tiles[(t + 1) & 1], true);
+    __syncthreads();
+  }
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  if (lq < V) {
+    if (kg < 2) {
+      f32x4 o;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = acc[r] / l * AB_SCALE;
+      *(f32x4*)(dqkv + qtok * row + h * 8 + 4 * kg) = o;
+    }
+    if (kg == 0) *(f32x4*)(rowstat + (((size_t)n * NH + h) * V + lq) * 4) = (f32x4){m, l, D, 0.f};
+  }
+}
+
+__global__ __launch_bounds__(256) void attention_bwd_mfma_k_kernel(const float* __restrict__ qkv, const float* __restrict__ dy,
+                                                                   const float* __restrict__ rowstat, float* __restrict__ dqkv,
+                                                                   int T, int W, int vh, int vw, int C) {
+  __shared__ AbQueryTile tiles[2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = lane & 15, kg = lane >> 4;
+  const int n = blockIdx.z, h = blockIdx.y, NH = C / 8, V = vh * vw;
+  const size_t row = (size_t)3 * C;
+  const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const int lk = blockIdx.x * 64 + wave * 16 + j;
+  const size_t ktok = (size_t)n * T + ab_token(lk < V ? lk : V - 1, W, vw);
+  // B operands of S = Q K^T and dP = dY V^T: lane (key j, k' = kg), step s uses dim 2 kg + s
+  const float* kp = qkv + ktok * row + C + h * 8 + 2 * kg;
+  const float ka = kp[0], kb = kp[1], va = kp[C], vb = kp[C + 1];
+  const float* rs = rowstat + ((size_t)n * NH + h) * V * 4;
+
+  // staging of one query tile: threads 0..127 the q row of query tid, threads 128..255 the dy row and the statistics
+  const int srow = tid & (AB_QT - 1), shalf = tid >> 7;
+  const int ntiles = (V + AB_QT - 1) / AB_QT;
+  f32x4 s0, s1, sst;
+  auto stage_load = [&](int t) {
+    const int li = t * AB_QT + srow;
+    s0 = s1 = sst = zero4;
+    if (li < V) {
+      const size_t tok = (size_t)n * T + ab_token(li, W, vw);
+      const float* p = shalf ? dy + tok * C + h * 8 : qkv + tok * row + h * 8;
+      s0 = *(const f32x4*)p;
+      s1 = *(const f32x4*)(p + 4);
+      if (shalf) {
+        const f32x4 st = *(const f32x4*)(rs + (size_t)li * 4);
+        sst = (f32x4){st[0], 1.0f / st[1], st[2], 0.f};
+      }
+    }
+  };
+  auto stage_store = [&](AbQueryTile& tl) {
+    float(*rows)[8] = shalf ? tl.dy : tl.q;
+    float(*cols)[AB_QT + AB_PAD] = shalf ? tl.dyt : tl.qt;
+    *(f32x4*)&rows[srow][0] = s0;
+    *(f32x4*)&rows[srow][4] = s1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      cols[e][srow] = s0[e];
+      cols[4 + e][srow] = s1[e];
+    }
+    if (shalf) tl.st[srow] = sst;
+  };
+
+  f32x4 dk = zero4, dv = zero4;  // dk~^T / dv^T[dd = 4 kg + r][key j]  (kg >= 2: padding rows)
+  stage_load(0);
+  stage_store(tiles[0]);
+  __syncthreads();
+  for (int t = 0; t < ntiles; ++t) {
+    const AbQueryTile& tl = tiles[t & 1];
+    if (t + 1 < ntiles) stage_load(t + 1);
+    const int nq = (V - t * AB_QT) < AB_QT ? (V - t * AB_QT) : AB_QT;
+    for (int i0 = 0; i0 < nq; i0 += 16) {
+      // S[query 4 kg + r][key j]: A = Q[query i = lane & 15][dim], B = K^T[dim][key j]
+      f32x4 s = __builtin_amdgcn_mfma_f32_16x16x4f32(tl.q[i0 + j][2 * kg], ka, zero4, 0, 0, 0);
+      s = __builtin_amdgcn_mfma_f32_16x16x4f32(tl.q[i0 + j][2 * kg + 1], kb, s, 0, 0, 0);
+      f32x4 dp = __builtin_amdgcn_mfma_f32_16x16x4f32(tl.dy[i0 + j][2 * kg], va, zero4, 0, 0, 0);
+      dp = __builtin_amdgcn_mfma_f32_16x16x4f32(tl.dy[i0 + j][2 * kg + 1], vb, dp, 0, 0, 0);
+      f32x4 p, ds;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const f32x4 st = tl.st[i0 + 4 * kg + r];
+        p[r] = __builtin_amdgcn_exp2f((s[r] - st[0]) * AB_EXP_SCALE) * st[1];
+        ds[r] = p[r] * (dp[r] - st[2]);
+      }
+      // A = Q^T / dY^T[dd i = lane & 15][query 4 kg + u], B = dS / P[query][key j]
+      f32x4 qf = zero4, df = zero4;
+      if (j < 8) {
+        qf = *(const f32x4*)&tl.qt[j][i0 + 4 * kg];
+        df = *(const f32x4*)&tl.dyt[j][i0 + 4 * kg];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        dk = __builtin_amdgcn_mfma_f32_16x16x4f32(qf[u], ds[u], dk, 0, 0, 0);
+        dv = __builtin_amdgcn_mfma_f32_16x16x4f32(df[u], p[u], dv, 0, 0, 0);
+      }
+    }
+    if (t + 1 < ntiles) stage_store(tiles[(t + 1) & 1]);
+    __syncthreads();
+  }
+  if (lk < V && kg < 2) {
+    float* o = dqkv + ktok * row + C + h * 8 + 4 * kg;
+    *(f32x4*)o = dk * AB_SCALE;
+    *(f32x4*)(o + C) = dv;
+  }
+}
+
+extern "C" int dmd_attention_bwd_mfma(const float* qkv, const float* y, const float* dy, float* dqkv, float* workspace, int N, int H,
+                                      int W, int valid_h, int valid_w, int C, int head_dim, dmd_stream_t stream) {
+  DMD_CHECK_ARG(qkv && y && dy && dqkv && workspace, "attention_bwd_mfma: null");
+  DMD_CHECK_ARG(head_dim == 8 && C % 8 == 0 && N > 0 && H > 0 && W > 0,
+                "attention_bwd_mfma: head_dim must be 8 (got %d), C %% 8 == 0 (C=%d), N, H, W > 0", head_dim, C);
+  DMD_CHECK_ARG(valid_h > 0 && valid_h <= H && valid_w > 0 && valid_w <= W, "attention_bwd_mfma: valid extent %d x %d of %d x %d",
+                valid_h, valid_w, H, W);
+  hipStream_t st = (hipStream_t)stream;
+  const int T = H * W, V = valid_h * valid_w;
+  const int nbv = (V + 63) / 64, nbm = (T - V + 255) / 256;
+  hipLaunchKernelGGL(attention_bwd_mfma_q_kernel, dim3(nbv + nbm, C / 8, N), dim3(256), 0, st, qkv, y, dy, dqkv, workspace, T, W,
+                     valid_h, valid_w, C, nbv);
+  hipLaunchKernelGGL(attention_bwd_mfma_k_kernel, dim3(nbv, C / 8, N), dim3(256), 0, st, qkv, dy, (const float*)workspace, dqkv, T, W,
+                     valid_h, valid_w, C);
   DMD_LAUNCH_CHECK();
   return 0;
 }

@@ -227,6 +227,15 @@ int dmd_attention_bwd(const float* qkv, const float* y, const float* dy, float* 
  * is bitwise dmd_attention_bwd's (same summation order).  workspace: dmd_attention_bwd_workspace_floats(N, H * W, C). */
 int dmd_attention_bwd_valid(const float* qkv, const float* y, const float* dy, float* dqkv, float* workspace, int N, int H, int W,
                             int valid_h, int valid_w, int C, int head_dim, dmd_stream_t stream);
+/* (ABI v11 addition) The same gradient on the fp32 matrix cores (v_mfma_f32_16x16x4_f32, exact fp32 operands), for long token
+ * grids: two tiled kernels of 64 queries (64 keys) per workgroup that stream the other side in LDS tiles of 256 tokens, two
+ * passes over the keys for the row maximum and the weights, no atomics, every sum in a fixed order (run-to-run bitwise).
+ * Arguments, extent convention, margins (never read; dqkv written as ZERO there) and workspace size are dmd_attention_bwd_valid's;
+ * the full grid of T tokens is H = 1, W = T, valid = (1, T), and the whole-grid call (H, W, H, W) is bitwise that one.  The
+ * result differs from dmd_attention_bwd's in rounding only (weights by exp2 of the fp32 score difference; same error against
+ * float64: profiles/attention_bwd_mfma_precision.txt).  Any valid token count >= 1. */
+int dmd_attention_bwd_mfma(const float* qkv, const float* y, const float* dy, float* dqkv, float* workspace, int N, int H, int W,
+                           int valid_h, int valid_w, int C, int head_dim, dmd_stream_t stream);
 
 /* ---- dmd_lowres_chain: a whole chain of ResBlocks at the 8x8 level of the denoiser's U-Net in ONE launch ----
  * Replaces, for H = W = 8 and 64 channels, the launches of the deepest level of UNet.forward (reference blocks.py:232-246:
