@@ -54,12 +54,15 @@ class RunCtx:
     GEMM -- they all consume the same cond vector, blocks.py:171-177)."""
 
     def __init__(self, cache: E.PackCache, film: Optional["FilmTable"] = None, table: Optional[Tensor] = None,
-                 naive: Optional[bool] = None, precision: Optional[str] = None):
+                 naive: Optional[bool] = None, precision: Optional[str] = None, attn_precision: Optional[str] = None):
         self.cache = cache
         self.film = film
         self.table = table
         self.naive = naive
         self.precision = precision or E.WORLD_MODEL_PRECISION
+        # the attention cores' own switch (engine.ATTN_PRECISIONS); None: DIAMOND_ATTN_PRECISION at every launch.  `precision` above
+        # does not reach attention
+        self.attn_precision = attn_precision
         # cheaper (1-ulp v_exp/v_rcp) prologue math also for the shapes the split kernel does not cover
         self.fast_math = self.precision == "f16x2" and not naive
 
@@ -175,7 +178,7 @@ class SelfAttention2d(nn.Module):
         # back (reference blocks.py:64,72), recomputed from x + its statistics in the epilogue.
         qkv = E.conv2d([(x, nv.PROLOGUE_NORM, spec)], ctx.cache.conv_weight(self.qkv_proj), ctx.cache.conv_bias(self.qkv_proj),
                        3 * c, taps=1, want_stats=False, naive=ctx.naive, fast_math=ctx.fast_math, module=self.qkv_proj)
-        y = E.attention(qkv, c, c // self.n_head)
+        y = E.attention(qkv, c, c // self.n_head, precision=ctx.attn_precision)
         return E.conv2d([(Act(y, valid=x.valid), nv.PROLOGUE_NONE, None)], ctx.cache.conv_weight(self.out_proj),
                         ctx.cache.conv_bias(self.out_proj), c, taps=1, residual=x, residual_norm=spec, naive=ctx.naive,
                         fast_math=ctx.fast_math, module=self.out_proj)

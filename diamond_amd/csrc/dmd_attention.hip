@@ -1,5 +1,7 @@
 // dmd_attention -- softmax(q k^T / sqrt(d)) v for SelfAttention2d (models/blocks.py:62-72), head_dim d = 8 (ATTN_HEAD_DIM
-// blocks.py:14), K / V tiles of 256 keys staged in LDS.  Two kernels, chosen by T alone (precision contract: include/diamond_hip.h):
+// blocks.py:14), K / V tiles of 256 keys staged in LDS.  dmd_attention has two kernels, chosen by T alone (precision contract:
+// include/diamond_hip.h); the caller's precision switch (engine.attention, DIAMOND_ATTN_PRECISION=f32) takes dmd_attention_valid's
+// attention_kernel or, for long token grids, dmd_attention_f32's attention_f32_tiled_kernel at the end of this file instead:
 //   T % 256 != 0, and every dmd_attention_valid: attention_kernel below -- exact fp32, flash-style ONLINE softmax, QK^T and PV on
 //                 v_mfma_f32_16x16x4_f32;
 //   T % 256 == 0 (256 = the default denoiser's 16x16 level, training forward included; 1024 / 4096 at 256x256):
@@ -950,6 +952,217 @@ extern "C" int dmd_attention_bwd_mfma(const float* qkv, const float* y, const fl
                      valid_h, valid_w, C, nbv);
   hipLaunchKernelGGL(attention_bwd_mfma_k_kernel, dim3(nbv, C / 8, N), dim3(256), 0, st, qkv, dy, (const float*)workspace, dqkv, T, W,
                      valid_h, valid_w, C);
+  DMD_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// dmd_attention_f32 -- the EXACT forward for long token grids (engine.attention under DIAMOND_ATTN_PRECISION=f32, from
+// ATTN_F32_TILED_MIN_T valid tokens on): softmax(q k^T / sqrt(d)) v on v_mfma_f32_16x16x4_f32 with exact fp32 operands, fp32
+// throughout (IEEE subtraction, multiplication, sums and division; the exponential is v_exp_f32, about 1 ulp, as in
+// attention_bwd_mfma_q_kernel).  attention_f32_tiled_kernel is attention_bwd_mfma_q_kernel's forward half: 4 waves x AT_QG groups of 16 queries, K
+// (pass 2: K and V^T) tiles of 256 keys double-buffered in LDS and staged by all 256 threads (the next tile is loaded into
+// registers before the compute loop and stored behind it), tokens addressed by their VALID index (ab_token), S^T = K Q^T so that
+// lane (j = lane & 15, kg = lane >> 4) owns keys {4 kg + r} of ONE query j.  TWO passes over the keys: the first finds the row
+// maximum m of the raw q . k, the second forms p = 2^((q . k - m) log2(e) / sqrt(d)), the row sum l (per lane in key order, the
+// four lanes of a query combined once at the end) and O^T[dim][query] += V^T P^T with the four p directly as the B operand
+// (attention_kernel's k-remap); out = O / l.  Inside the key loop there is no rescale, no shuffle, no division and no integer
+// division; no atomics anywhere: every sum has a fixed order that depends on the (image, head)'s own tokens only.  Keys behind the
+// last valid one get the score -inf (their LDS rows are zero).  The workgroups behind the valid ones write the rows of `out` outside
+// the extent as +0.  Lanes of a partial last block compute on the last valid token and write nothing.
+// AT_QG (16-query groups per wave, which share the wave's LDS reads of K and V^T) and AT_UNROLL (16-key blocks of a whole tile per
+// loop iteration; 1 = the rolled loop) were measured side by side: profiles/attention_f32_tiled.json, "query_groups_per_wave";
+// HISTORY.md has the figures, what made a difference (whole tiles have a loop of their own: constant trip count, no key mask) and
+// what did not (the unroll factor).
+// ------------------------------------------------------------------------------------------------
+#ifndef AT_QG
+#define AT_QG 2
+#endif
+#ifndef AT_UNROLL
+#define AT_UNROLL 4  // 16-key blocks of a whole tile per loop iteration
+#endif
+
+struct AtKeyTile {
+  float k[AB_KT][8];
+  float vt[8][AB_KT + AB_PAD];  // V^T[dim][key]
+};
+
+__global__ __launch_bounds__(256) void attention_f32_tiled_kernel(const float* __restrict__ qkv, float* __restrict__ out, int T, int W,
+                                                                  int vh, int vw, int C, int nbv) {
+  __shared__ AtKeyTile tiles[2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = lane & 15, kg = lane >> 4;
+  const int n = blockIdx.z, h = blockIdx.y, V = vh * vw;
+  const size_t row = (size_t)3 * C;
+  const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
+  if ((int)blockIdx.x >= nbv) {
+    // the m-th token outside the extent: rows < vh, columns >= vw first, then the rows >= vh
+    const int m = ((int)blockIdx.x - nbv) * 256 + tid, side = vh * (W - vw);
+    if (m >= T - V) return;
+    int r, c;
+    if (m < side) {
+      r = m / (W - vw);
+      c = vw + (m - r * (W - vw));
+    } else {
+      r = vh + (m - side) / W;
+      c = (m - side) - (r - vh) * W;
+    }
+    float* o = out + ((size_t)n * T + (size_t)r * W + c) * C + h * 8;
+    *(f32x4*)o = zero4;
+    *(f32x4*)(o + 4) = zero4;
+    return;
+  }
+  const float* base = qkv + (size_t)n * T * row;
+  // B operand of S^T = K Q^T per 16-query group: lane (query j, k' = kg), step s uses dim 2 kg + s
+  int lq[AT_QG];
+  size_t qtok[AT_QG];
+  float qa[AT_QG], qb[AT_QG];
+#pragma unroll
+  for (int g = 0; g < AT_QG; ++g) {
+    lq[g] = (blockIdx.x * 4 + wave) * (16 * AT_QG) + g * 16 + j;
+    qtok[g] = (size_t)n * T + ab_token(lq[g] < V ? lq[g] : V - 1, W, vw);
+    const float* qp = qkv + qtok[g] * row + h * 8 + 2 * kg;
+    qa[g] = qp[0];
+    qb[g] = qp[1];
+  }
+
+  const int ntiles = (V + AB_KT - 1) / AB_KT;
+  f32x4 sk0, sk1, sv0, sv1;
+  auto stage_load = [&](int t, bool with_v) {
+    const int lk = t * AB_KT + tid;
+    sk0 = sk1 = sv0 = sv1 = zero4;
+    if (lk < V) {
+      const float* kp = base + (size_t)ab_token(lk, W, vw) * row + C + h * 8;
+      sk0 = *(const f32x4*)kp;
+      sk1 = *(const f32x4*)(kp + 4);
+      if (with_v) {
+        sv0 = *(const f32x4*)(kp + C);
+        sv1 = *(const f32x4*)(kp + C + 4);
+      }
+    }
+  };
+  auto stage_store = [&](AtKeyTile& tl, bool with_v) {
+    *(f32x4*)&tl.k[tid][0] = sk0;
+    *(f32x4*)&tl.k[tid][4] = sk1;
+    if (with_v) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        tl.vt[e][tid] = sv0[e];
+        tl.vt[4 + e][tid] = sv1[e];
+      }
+    }
+  };
+  // S^T block of 16 keys: s[r] = q_j . k_{k0 + 4 kg + r} from the lane's K fragment, -inf behind the tile's nk keys
+  auto scores = [&](float ka, float kb, int g, int k0, int nk) -> f32x4 {
+    f32x4 s = __builtin_amdgcn_mfma_f32_16x16x4f32(ka, qa[g], zero4, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_16x16x4f32(kb, qb[g], s, 0, 0, 0);
+    if (k0 + 16 > nk) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (k0 + 4 * kg + r >= nk) s[r] = -INFINITY;
+    }
+    return s;
+  };
+
+  // ---------------- pass 1: row maxima of q . k ----------------
+  float m[AT_QG];
+#pragma unroll
+  for (int g = 0; g < AT_QG; ++g) m[g] = -INFINITY;
+  stage_load(0, false);
+  stage_store(tiles[0], false);
+  __syncthreads();
+  for (int t = 0; t < ntiles; ++t) {
+    const AtKeyTile& tl = tiles[t & 1];
+    if (t + 1 < ntiles) stage_load(t + 1, false);
+    const int nk = (V - t * AB_KT) < AB_KT ? (V - t * AB_KT) : AB_KT;
+    auto block = [&](int k0, int nk) {
+      const float ka = tl.k[k0 + j][2 * kg], kb = tl.k[k0 + j][2 * kg + 1];
+#pragma unroll
+      for (int g = 0; g < AT_QG; ++g) {
+        const f32x4 s = scores(ka, kb, g, k0, nk);
+        m[g] = af_max3(af_max3(m[g], s[0], s[1]), s[2], s[3]);
+      }
+    };
+    if (nk == AB_KT) {  // a whole tile: constant trip count, no key mask (the same operations in the same order)
+#pragma unroll AT_UNROLL
+      for (int k0 = 0; k0 < AB_KT; k0 += 16) block(k0, AB_KT);
+    } else {
+      for (int k0 = 0; k0 < nk; k0 += 16) block(k0, nk);
+    }
+    if (t + 1 < ntiles) stage_store(tiles[(t + 1) & 1], false);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int g = 0; g < AT_QG; ++g) {
+    m[g] = fmaxf(m[g], __shfl_xor(m[g], 16, 64));
+    m[g] = fmaxf(m[g], __shfl_xor(m[g], 32, 64));
+  }
+
+  // ---------------- pass 2: weights, row sums, O^T[dim][query] += V^T P^T ----------------
+  f32x4 acc[AT_QG];  // O~^T[dd = 4 kg + r][query j]  (kg >= 2: padding rows)
+  float l[AT_QG];
+#pragma unroll
+  for (int g = 0; g < AT_QG; ++g) {
+    acc[g] = zero4;
+    l[g] = 0.f;
+  }
+  stage_load(0, true);
+  stage_store(tiles[0], true);
+  __syncthreads();
+  for (int t = 0; t < ntiles; ++t) {
+    const AtKeyTile& tl = tiles[t & 1];
+    if (t + 1 < ntiles) stage_load(t + 1, true);
+    const int nk = (V - t * AB_KT) < AB_KT ? (V - t * AB_KT) : AB_KT;
+    auto block = [&](int k0, int nk) {
+      const float ka = tl.k[k0 + j][2 * kg], kb = tl.k[k0 + j][2 * kg + 1];
+      // A = V^T[dd i = lane & 15][key 4 kg + u], B = P^T[key][query j] = p[u]
+      f32x4 vf = zero4;
+      if (j < 8) vf = *(const f32x4*)&tl.vt[j][k0 + 4 * kg];
+#pragma unroll
+      for (int g = 0; g < AT_QG; ++g) {
+        const f32x4 s = scores(ka, kb, g, k0, nk);
+        f32x4 p;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) p[r] = __builtin_amdgcn_exp2f((s[r] - m[g]) * AB_EXP_SCALE);
+        l[g] += (p[0] + p[1]) + (p[2] + p[3]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[u], p[u], acc[g], 0, 0, 0);
+      }
+    };
+    if (nk == AB_KT) {
+#pragma unroll AT_UNROLL
+      for (int k0 = 0; k0 < AB_KT; k0 += 16) block(k0, AB_KT);
+    } else {
+      for (int k0 = 0; k0 < nk; k0 += 16) block(k0, nk);
+    }
+    if (t + 1 < ntiles) stage_store(tiles[(t + 1) & 1], true);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int g = 0; g < AT_QG; ++g) {
+    float ls = l[g];
+    ls += __shfl_xor(ls, 16, 64);
+    ls += __shfl_xor(ls, 32, 64);
+    if (lq[g] < V && kg < 2) {
+      f32x4 o;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = acc[g][r] / ls;
+      *(f32x4*)(out + qtok[g] * C + h * 8 + 4 * kg) = o;
+    }
+  }
+}
+
+extern "C" int dmd_attention_f32(const float* qkv, float* out, int N, int H, int W, int valid_h, int valid_w, int C, int head_dim,
+                                 dmd_stream_t stream) {
+  DMD_CHECK_ARG(qkv && out, "attention_f32: null");
+  DMD_CHECK_ARG(head_dim == 8, "attention_f32: head_dim must be 8 (ATTN_HEAD_DIM), got %d", head_dim);
+  DMD_CHECK_ARG(C % 8 == 0 && C > 0 && N > 0 && H > 0 && W > 0, "attention_f32: need C %% 8 == 0, N, H, W > 0 (H=%d W=%d C=%d)", H, W, C);
+  DMD_CHECK_ARG(valid_h > 0 && valid_h <= H && valid_w > 0 && valid_w <= W, "attention_f32: valid extent %d x %d of %d x %d", valid_h,
+                valid_w, H, W);
+  const int T = H * W, V = valid_h * valid_w;
+  const int nbv = (V + 64 * AT_QG - 1) / (64 * AT_QG), nbm = (T - V + 255) / 256;
+  hipLaunchKernelGGL(attention_f32_tiled_kernel, dim3(nbv + nbm, C / 8, N), dim3(256), 0, (hipStream_t)stream, qkv, out, T, W, valid_h,
+                     valid_w, C, nbv);
   DMD_LAUNCH_CHECK();
   return 0;
 }

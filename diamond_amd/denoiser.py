@@ -90,9 +90,12 @@ class Denoiser(nn.Module):
     @torch.no_grad()
     def compute_model_output(self, noisy_next_obs: Tensor, obs: Tensor, act: Tensor, sigma: Union[Tensor, float],
                              naive: Optional[bool] = None, precision: Optional[str] = None,
-                             ring: Optional[Tuple[int, int]] = None, table: Optional[Tensor] = None) -> Tensor:
+                             ring: Optional[Tuple[int, int]] = None, table: Optional[Tensor] = None,
+                             attn_precision: Optional[str] = None) -> Tensor:
         """F = inner_model(x * c_in, c_noise, obs / sigma_data, act)  (reference :74-77).
-        precision: None (engine.WORLD_MODEL_PRECISION) | "f32" | "f16x2".
+        precision: None (engine.WORLD_MODEL_PRECISION) | "f32" | "f16x2": the convolutions'.
+        attn_precision: None (DIAMOND_ATTN_PRECISION, default "f16x2") | "f32" | "f16x2": the attention cores' (engine.attention);
+        reference-width arithmetic needs both set to "f32".
         ring = (obs_head, act_head): `obs` is then the PHYSICAL ring (N, T, C, H, W) of conditioning frames and `act`
         the physical (N, T) ring of actions of a WorldModelEnv (logical step t at slot (head + t) % T); the ring
         order is resolved inside dmd_edm_pack_input / dmd_cond_embed, nothing is rolled or copied."""
@@ -121,7 +124,7 @@ class Denoiser(nn.Module):
                  "dmd_edm_pack_input")
         # (table: this forward's FiLM table, if the caller computed the tables of several steps at once -- film_tables below)
         cvec = self.inner_model.cond_vector(cond, stride, act, act_head) if table is None else None
-        out = self.inner_model.run(packed, cvec, naive, precision, table=table, valid=valid)
+        out = self.inner_model.run(packed, cvec, naive, precision, table=table, valid=valid, attn_precision=attn_precision)
         return E.crop_to_valid(out, valid, nchw=True)
 
     @torch.no_grad()
@@ -145,8 +148,9 @@ class Denoiser(nn.Module):
 
     @torch.no_grad()
     def denoise(self, noisy_next_obs: Tensor, sigma: Union[Tensor, float], obs: Tensor, act: Tensor,
-                ring: Optional[Tuple[int, int]] = None, table: Optional[Tensor] = None) -> Tensor:
-        f = self.compute_model_output(noisy_next_obs, obs, act, sigma, ring=ring, table=table)
+                ring: Optional[Tuple[int, int]] = None, table: Optional[Tensor] = None,
+                attn_precision: Optional[str] = None) -> Tensor:
+        f = self.compute_model_output(noisy_next_obs, obs, act, sigma, ring=ring, table=table, attn_precision=attn_precision)
         return self.wrap_model_output(noisy_next_obs, f, sigma)
 
     # at most this many bytes of FiLM tables at once (a 50-step schedule at batch 256 would be 367 MB: computed per step instead)
@@ -186,8 +190,10 @@ class Denoiser(nn.Module):
         return c_in, c_out, c_skip, c_noise
 
     def model_output_with_grad(self, noisy_next_obs: Tensor, obs: Tensor, act: Tensor, conditioners,
-                               precision: Optional[str] = None) -> Tensor:
-        """F = inner_model(x * c_in, c_noise, obs / sigma_data, act) (:74-77) differentiable w.r.t. every parameter:
+                               precision: Optional[str] = None, attn_precision: Optional[str] = None) -> Tensor:
+        """F = inner_model(x * c_in, c_noise, obs / sigma_data, act) (:74-77) differentiable w.r.t. every parameter
+        (attn_precision: the recorded forward's attention cores, as in compute_model_output -- with "f32" the attention backward
+        differentiates around an exact y):
         the U-Net forward runs on the HIP kernels while its launches are recorded, its backward is
         unet_train.UNetTrainFn; the cond vector / FiLM table (three small GEMMs) run on dmd_linear through lstm_native.LinearFn,
         whose backward is dmd_linear as well (torch autograd only carries the gradient between the nodes)."""
@@ -227,7 +233,7 @@ class Denoiser(nn.Module):
         table = LinearFn.apply(im._cache, cond, w_cat, b_cat)
         if self._train_params is None:
             self._train_params = UT.trainable_unet_params(im)
-        out = UT.UNetTrainFn.apply(im, packed, table, precision or UT.TRAIN_PRECISION, valid, *self._train_params)
+        out = UT.UNetTrainFn.apply(im, packed, table, precision or UT.TRAIN_PRECISION, valid, attn_precision, *self._train_params)
         return out if valid is None else out[:, :, :h, :w]
 
     def forward(self, batch):

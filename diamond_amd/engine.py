@@ -825,10 +825,63 @@ def nhwc_to_nchw(x: Tensor, c: Optional[int] = None) -> Tensor:
     return out
 
 
-def attention(qkv: Act, c: int, head_dim: int = 8) -> Tensor:
+# Arithmetic of the attention cores (SelfAttention2d; the 8x8 dmd_lowres_chain / chain32 launches carry their own core, which is on
+# fp32 operands already):
+#   "f16x2": dmd_attention's routing by T alone -- the split-fp16 two-pass kernel at T % 256 == 0 (default);
+#   "f32"  : exact fp32 operands everywhere: dmd_attention_f32 (attention_f32_tiled_kernel) from ATTN_F32_TILED_MIN_T VALID tokens
+#            on, attention_kernel (dmd_attention_valid, over the real or the whole-grid extent) below that.
+# DIAMOND_ATTN_PRECISION is read at every call that does not name a precision; it is a switch of its own: DIAMOND_CONV_PRECISION=f32
+# does not imply it, and reference-width arithmetic needs both.
+# ATTN_F32_TILED_MIN_T: measured (profiles/attention_f32_tiled.json, "derived_threshold": the smallest measured token count from
+# which the tiled kernel beats attention_kernel at every measured shape by more than the block-to-block spread; 256 tokens were
+# measured at N = 8 and 32, and an 18 x 20 extent of a 32 x 32 grid stands for the valid-extent grids between 256 and 1023 tokens --
+# other extents in that range are not measured: attention_kernel walks the whole padded grid, the tiled kernel the valid tokens
+# only, so by the code the gap can only widen there).  Nothing below 256 tokens was measured, so nothing below it is routed.
+# DIAMOND_ATTN_F32_MIN_T=n overrides it (read at every call), 0 = never the tiled kernel.
+ATTN_PRECISIONS = ("f16x2", "f32")
+ATTN_F32_TILED_MIN_T = 256
+
+
+def attn_precision(precision: Optional[str] = None) -> str:
+    p = precision or os.environ.get("DIAMOND_ATTN_PRECISION") or "f16x2"
+    if p not in ATTN_PRECISIONS:
+        raise ValueError(f"attention precision must be one of {ATTN_PRECISIONS}, got {p!r}")
+    return p
+
+
+def attn_f32_tiled_min_t() -> int:
+    v = os.environ.get("DIAMOND_ATTN_F32_MIN_T")
+    return ATTN_F32_TILED_MIN_T if v is None or v == "" else int(v)
+
+
+def _attention_f32(qkv: Act, out: Tensor, c: int, head_dim: int) -> None:
+    """the exact-fp32 routes of `attention`"""
+    n, h, w, _ = qkv.shape
+    vh, vw = qkv.valid if qkv.valid is not None else (1, h * w)
+    tv = vh * vw
+    min_t = attn_f32_tiled_min_t()
+    if min_t > 0 and tv >= min_t:  # long token grids: the tiled two-pass kernel, tokens addressed by their valid index
+        gh, gw = (h, w) if qkv.valid is not None else (1, h * w)
+        if nv.PROFILER is not None:  # QK^T and PV over the valid tokens: 2 x (2 T^2 d) per head
+            nv.PROFILER.annotate("attention_f32_tiled_kernel", 4.0 * n * tv * tv * c, 4.0 * n * tv * 4 * c)
+        nv.check(nv.lib().dmd_attention_f32(nv.fptr(qkv.t), nv.fptr(out), n, gh, gw, vh, vw, c, head_dim, nv.stream()), "dmd_attention_f32")
+        return
+    vh, vw = qkv.valid if qkv.valid is not None else (h, w)
+    if nv.PROFILER is not None:
+        nv.PROFILER.annotate("attention_kernel", 4.0 * n * (vh * vw) * (h * w) * c, 4.0 * n * h * w * 4 * c)
+    nv.check(nv.lib().dmd_attention_valid(nv.fptr(qkv.t), nv.fptr(out), n, h, w, vh, vw, c, head_dim, nv.stream()), "dmd_attention_valid")
+
+
+def attention(qkv: Act, c: int, head_dim: int = 8, precision: Optional[str] = None) -> Tensor:
+    """precision: None (DIAMOND_ATTN_PRECISION, default "f16x2") | "f16x2" | "f32" (see ATTN_PRECISIONS above)"""
     n, h, w, c3 = qkv.shape
     assert c3 == 3 * c
     out = torch.empty(n, h, w, c, device=qkv.t.device, dtype=torch.float32)
+    if attn_precision(precision) == "f32":
+        _attention_f32(qkv, out, c, head_dim)
+        if TAPE is not None:
+            TAPE.append(AttnRecord(qkv, out, c, head_dim, qkv.valid))
+        return out
     if qkv.valid is not None:  # keys outside the valid extent stay out of the softmax
         nv.check(nv.lib().dmd_attention_valid(nv.fptr(qkv.t), nv.fptr(out), n, h, w, qkv.valid[0], qkv.valid[1], c, head_dim, nv.stream()),
                  "dmd_attention_valid")

@@ -96,8 +96,10 @@ class InnerModel(nn.Module):
         return [table[i * n:(i + 1) * n] for i in range(k)]
 
     def run(self, packed_in: Tensor, cond: Optional[Tensor], naive: Optional[bool] = None, precision: Optional[str] = None,
-            table: Optional[Tensor] = None, valid: Optional[Tuple[int, int]] = None) -> Tensor:
+            table: Optional[Tensor] = None, valid: Optional[Tuple[int, int]] = None, attn_precision: Optional[str] = None) -> Tensor:
         """packed_in: NHWC16 [obs/sigma_data | noisy*c_in | 0]; returns F as NCHW (N,3,H,W).
+        attn_precision: the attention cores' arithmetic (engine.ATTN_PRECISIONS; None: DIAMOND_ATTN_PRECISION); `precision` is the
+        convolutions' and does not reach attention.
         table: the batched FiLM table if the caller already has it (the training path computes it under autograd).
         valid = (h, w): the image is that part of the (H, W) buffer, the rest of which is ZERO (engine.padded_extent): the
         reference's forward for sizes whose U-Net levels are not multiples of the kernels' tiles, including its
@@ -107,7 +109,7 @@ class InnerModel(nn.Module):
             self._film = FilmTable(self.unet)
         if table is None:
             table = self._film.compute(cond)
-        ctx = RunCtx(self._cache, self._film, table, naive, precision)
+        ctx = RunCtx(self._cache, self._film, table, naive, precision, attn_precision)
         x = E.conv2d([(E.Act(packed_in, needs_grad=False, valid=valid), nv.PROLOGUE_NONE, None)], self._cache.conv_weight(self.conv_in),
                      self._cache.conv_bias(self.conv_in), self.conv_in.out_channels, naive=naive, w_f16=ctx.w16(self.conv_in),
                      module=self.conv_in)

@@ -275,11 +275,11 @@ class UNetTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, inner, packed_in: Tensor, table: Tensor, precision: str, valid: Optional[Tuple[int, int]],
-                *params: Tensor) -> Tensor:
+                attn_precision: Optional[str], *params: Tensor) -> Tensor:
         assert E.TAPE is None, "nested recording"
         E.TAPE = []
         try:
-            out = inner.run(packed_in, None, precision=precision, table=table.detach(), valid=valid)
+            out = inner.run(packed_in, None, precision=precision, table=table.detach(), valid=valid, attn_precision=attn_precision)
             tape = E.TAPE
         finally:
             E.TAPE = None
@@ -292,7 +292,7 @@ class UNetTrainFn(torch.autograd.Function):
         pg, inv = scaled_backward(ctx.tape, ctx.inner._cache, d_out, ctx.table, use_f16=ctx.precision == "f16x2")
         ctx.tape = None  # free the saved activations
         grads = _unscale(pg, ctx.params, inv)
-        return (None, None, pg.dtable * inv, None, None, *grads)
+        return (None, None, pg.dtable * inv, None, None, None, *grads)
 
 
 def _unscale(pg: "_ParamGrads", params, inv: Tensor):

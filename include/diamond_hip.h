@@ -189,8 +189,14 @@ int dmd_linear(const dmd_linear_params* p, dmd_stream_t stream);
  *       fp32 evaluation of the formula gives.
  *   T % 256 == 0 (256 = the default denoiser's 16x16 level, 1024 / 4096 = the 256x256 configuration)   attention_f16x2_kernel:
  *       SPLIT-fp16 operands on the f16 MFMAs in TWO passes over the keys (row maxima, then weights / sums / PV).  The forward of
- *       the TRAINING step takes it too: there is no precision switch for attention (DIAMOND_CONV_PRECISION=f32 does not reach
- *       it), so dmd_attention_bwd differentiates around a split-fp16 y.  dmd_attention_valid never takes it.
+ *       the TRAINING step takes it too, so by default the attention backward differentiates around a split-fp16 y.
+ *       dmd_attention_valid never takes it.
+ * The precision switch is the CALLER's: dmd_attention itself keeps choosing by T alone.  DIAMOND_CONV_PRECISION=f32 does not reach
+ * attention; DIAMOND_ATTN_PRECISION=f32 (engine.attention's `precision`, the `attn_precision` keyword of the denoiser's inference
+ * and training paths) does: every attention core then runs on exact fp32 operands -- dmd_attention_f32 below from
+ * ATTN_F32_TILED_MIN_T valid tokens on, attention_kernel (through dmd_attention_valid) below that -- and the training backward
+ * differentiates around that exact y.  Reference-width arithmetic needs BOTH switches.  (The 8x8 dmd_lowres_chain / chain32
+ * launches carry their own attention core, which is on fp32 operands already.)
  * PRECISION CONTRACT of the two-pass kernel (tests/test_attention_precision.py walks its edges; measured table in
  * profiles/attention_precision.txt):
  *   * operands: k, v and q' = q * log2(e) / sqrt(d) are each held as two fp16 pieces x = h + l: off by at most
@@ -215,6 +221,21 @@ int dmd_attention(const float* qkv, float* out, int N, int T, int C, int head_di
  * do not take part in the softmax; outputs of queries outside it are unspecified */
 int dmd_attention_valid(const float* qkv, float* out, int N, int H, int W, int valid_h, int valid_w, int C, int head_dim,
                         dmd_stream_t stream);
+/* (ABI v11 addition) The exact forward for long token grids: attention_f32_tiled_kernel, exact fp32 operands on
+ * v_mfma_f32_16x16x4_f32, fp32 throughout (IEEE arithmetic; the exponential is v_exp_f32, about 1 ulp), TWO passes over the keys (row maximum of the raw q . k, then
+ * p = 2^((q . k - m) log2(e) / sqrt(d)), row sum, O += P V; out = O / l), K / V tiles of 256 keys double-buffered in LDS, no online
+ * rescale, no atomics: run-to-run bitwise, and an (image, head)'s output does not depend on N or on the other heads.
+ * Extent convention of dmd_attention_bwd_mfma: tokens are addressed by their valid index li <-> (li / valid_w) * W + li % valid_w,
+ * the work is sized by valid_h * valid_w, nothing outside the extent is read (the margins of qkv may hold anything, NaN / Inf
+ * included) and the rows of `out` outside the extent are written as +0.  The full grid of T tokens is H = 1, W = T,
+ * valid = (1, T); the whole-grid call (H, W, H, W) is bitwise that one.  Any valid token count >= 1 (no T % 64 condition).  d == 8.
+ * PRECISION CONTRACT, beside the two-pass split kernel's above: operands are the fp32 numbers themselves -- the full fp32 range,
+ * no floor, no rebalancing; a finite operand beyond 65504 is simply computed; NaN / +-Inf operands give what an fp32 evaluation of
+ * the formula gives (a key whose score is -Inf drops out of its row; +Inf or NaN scores make their row NaN; a non-finite v element
+ * stays in its dim).  Error against float64 within K_TILED x that of a float32 CPU evaluation per (image, head)
+ * (tests/test_attention_f32_tiled.py, profiles/attention_f32_tiled_precision.txt); differs from attention_kernel in rounding only. */
+int dmd_attention_f32(const float* qkv, float* out, int N, int H, int W, int valid_h, int valid_w, int C, int head_dim,
+                      dmd_stream_t stream);
 /* Backward of dmd_attention (autograd of blocks.py:66-71 under the denoiser training loss, denoiser.py:93-122):
  * y = the forward's output, dy its gradient -> dqkv (N, T, 3C) in the qkv layout.  workspace: dmd_attention_bwd_workspace_floats. */
 int64_t dmd_attention_bwd_workspace_floats(int N, int T, int C);
