@@ -1,12 +1,17 @@
-// dmd_attention -- softmax(q k^T / sqrt(d)) v for SelfAttention2d (models/blocks.py:62-72), head_dim d = 8 (ATTN_HEAD_DIM
-// blocks.py:14), K / V tiles of 256 keys staged in LDS.  dmd_attention has two kernels, chosen by T alone (precision contract:
-// include/diamond_hip.h); the caller's precision switch (engine.attention, DIAMOND_ATTN_PRECISION=f32) takes dmd_attention_valid's
-// attention_kernel or, for long token grids, dmd_attention_f32's attention_f32_tiled_kernel at the end of this file instead:
-//   T % 256 != 0, and every dmd_attention_valid: attention_kernel below -- exact fp32, flash-style ONLINE softmax, QK^T and PV on
-//                 v_mfma_f32_16x16x4_f32;
-//   T % 256 == 0 (256 = the default denoiser's 16x16 level, training forward included; 1024 / 4096 at 256x256):
-//                 attention_f16x2_kernel further down -- split-fp16 operands on v_mfma_f32_16x16x32_f16, TWO passes over the
-//                 keys, no online rescale.
+// Attention of SelfAttention2d (models/blocks.py:62-72): softmax(q k^T / sqrt(d)) v and its gradient, head_dim d = 8 (ATTN_HEAD_DIM,
+// blocks.py:14).  qkv / dqkv are NHWC (N, T, 3C): q | k | v channel thirds, head h = channels [8h, 8h + 8).  Precision contracts:
+// include/diamond_hip.h; which entry point the host calls: engine.attention (forward), grad_ops.attention_bwd (backward).
+//   entry point              kernel(s)                                      when
+//   dmd_attention            attention_f16x2_kernel                         T % 256 == 0: split-fp16 operands, two passes over the keys
+//                            attention_kernel                               any other T % 64 == 0: exact fp32, online softmax
+//   dmd_attention_valid      attention_kernel                               always; keys outside the extent are masked
+//   dmd_attention_f32        attention_f32_tiled_kernel                     always: exact fp32, two passes, over the valid tokens
+//   dmd_attention_bwd        attention_bwd_rows_kernel + _cols_kernel       always: the extent (1, T, 1, T) of a (1, T) grid
+//   dmd_attention_bwd_valid  attention_bwd_rows_kernel + _cols_kernel       always: the extent as given
+//   dmd_attention_bwd_mfma   attention_bwd_mfma_q_kernel + _k_kernel        always: fp32 matrix cores, the extent as given
+// EXTENT CONVENTION of every kernel but the first two: only rows < vh, columns < vw of a row-major (H, W) token grid exist
+// (dmd_conv_params: VALID EXTENT); tokens are addressed by their valid index (ab_token), nothing outside the extent is read, and the
+// whole grid of T tokens is the extent (1, T, 1, T) of a (1, T) grid.
 //
 // attention_kernel:
 // Layout trick: compute the TRANSPOSED score block S^T[key][query] = K Q^T so that a lane
@@ -24,6 +29,31 @@
 
 #define ATT_KB 256          // keys per LDS tile
 #define ATT_VSTRIDE (ATT_KB + 16)
+
+// token of valid index li: the li-th token, in row-major order, of the (vh, vw) extent of an (H, W) grid
+__device__ __forceinline__ int ab_token(int li, int W, int vw) {
+  const int r = li / vw;
+  return r * W + (li - r * vw);
+}
+// the m-th token OUTSIDE the extent, m < H W - vh vw: rows < vh, columns >= vw first, then the rows >= vh (vw == W: side is 0 and
+// nothing divides by W - vw)
+__device__ __forceinline__ int ab_margin_token(int m, int W, int vh, int vw) {
+  const int side = vh * (W - vw);
+  if (m >= side) return vh * W + (m - side);
+  const int r = m / (W - vw);
+  return r * W + vw + (m - r * (W - vw));
+}
+
+// The argument checks the entry points share (`who` names the entry point in the message); one over T tokens with no grid of its
+// own passes the whole-grid extent (1, T, 1, T).  0 if they hold.
+static int att_check_args(const char* who, bool pointers, int N, int H, int W, int valid_h, int valid_w, int C, int head_dim) {
+  DMD_CHECK_ARG(pointers, "%s: null", who);
+  DMD_CHECK_ARG(head_dim == 8, "%s: head_dim must be 8 (ATTN_HEAD_DIM), got %d", who, head_dim);
+  DMD_CHECK_ARG(C > 0 && C % 8 == 0 && N > 0 && H > 0 && W > 0, "%s: need C %% 8 == 0, N, H, W > 0 (N=%d H=%d W=%d C=%d)", who, N, H, W, C);
+  DMD_CHECK_ARG(valid_h > 0 && valid_h <= H && valid_w > 0 && valid_w <= W, "%s: valid extent %d x %d of %d x %d", who, valid_h, valid_w,
+                H, W);
+  return 0;
+}
 
 // Wp > 0 (dmd_attention_valid): the T tokens are a row-major (T / Wp) x Wp grid of which only rows < hv, columns < wv
 // exist; the other keys get the score -inf (token 0 always exists, so the running maximum is finite from the first block on).
@@ -372,9 +402,8 @@ __global__ __launch_bounds__(256, 2) void attention_f16x2_kernel(const float* __
 }
 
 extern "C" int dmd_attention(const float* qkv, float* out, int N, int T, int C, int head_dim, dmd_stream_t stream) {
-  DMD_CHECK_ARG(qkv && out, "attention: null");
-  DMD_CHECK_ARG(head_dim == 8, "attention: head_dim must be 8 (ATTN_HEAD_DIM), got %d", head_dim);
-  DMD_CHECK_ARG(C % 8 == 0 && T % 64 == 0 && N > 0, "attention: need C %% 8 == 0, T %% 64 == 0 (T=%d C=%d)", T, C);
+  if (att_check_args("attention", qkv && out, N, 1, T, 1, T, C, head_dim)) return 1;
+  DMD_CHECK_ARG(T % 64 == 0, "attention: need T %% 64 == 0 (T=%d)", T);
   if (T % 256 == 0) {
     // whole 256-key tiles (256 tokens of the default 16x16 level, 1024 / 4096 of the 256x256 configuration): split-fp16 two-pass kernel
     hipLaunchKernelGGL(attention_f16x2_kernel, dim3(T / 256, C / 8, N), dim3(256), 0, (hipStream_t)stream, qkv, out, T, C,
@@ -392,11 +421,9 @@ extern "C" int dmd_attention(const float* qkv, float* out, int N, int T, int C, 
 // it do not take part in the softmax; the outputs of queries outside it are unspecified.
 extern "C" int dmd_attention_valid(const float* qkv, float* out, int N, int H, int W, int valid_h, int valid_w, int C, int head_dim,
                                    dmd_stream_t stream) {
-  DMD_CHECK_ARG(qkv && out, "attention: null");
-  DMD_CHECK_ARG(head_dim == 8, "attention: head_dim must be 8 (ATTN_HEAD_DIM), got %d", head_dim);
+  if (att_check_args("attention_valid", qkv && out, N, H, W, valid_h, valid_w, C, head_dim)) return 1;
   const int T = H * W;
-  DMD_CHECK_ARG(C % 8 == 0 && T % 64 == 0 && N > 0, "attention: need C %% 8 == 0, T %% 64 == 0 (T=%d C=%d)", T, C);
-  DMD_CHECK_ARG(valid_h > 0 && valid_h <= H && valid_w > 0 && valid_w <= W, "attention: valid extent %d x %d of %d x %d", valid_h, valid_w, H, W);
+  DMD_CHECK_ARG(T % 64 == 0, "attention_valid: need H W %% 64 == 0 (H=%d W=%d)", H, W);
   dim3 grid(T / 64, C / 8, N);
   hipLaunchKernelGGL(attention_kernel, grid, dim3(256), 0, (hipStream_t)stream, qkv, out, T, C, sqrtf((float)head_dim), W, valid_h, valid_w);
   DMD_LAUNCH_CHECK();
@@ -408,14 +435,18 @@ extern "C" int dmd_attention_valid(const float* qkv, float* out, int N, int H, i
 //   P = softmax(q k^T / sqrt(d)),  y = P v.   Given dy:
 //   D_i = dy_i . y_i ;  dP_ij = dy_i . v_j ;  dS_ij = P_ij (dP_ij - D_i)
 //   dq_i = sum_j dS_ij k_j / sqrt(d) ;  dk_j = sum_i dS_ij q_i / sqrt(d) ;  dv_j = sum_i P_ij dy_i
-// Two kernels, fp32 VALU, one thread per query (key) sweeping all T keys (queries) serially: the SMALL-T path (64 tokens at the 8x8
-// level, 256 at the default denoiser's 16x16 level, valid extents off the tile grid), where a step is bound by its launches rather
-// than by these FLOPs.  Long token grids (1024 / 4096 tokens of the 256x256 configuration) take dmd_attention_bwd_mfma at the end
-// of this file; unet_train.py chooses by the valid token count (ATTN_BWD_MFMA_MIN_T).
+// ONE pair of kernels, fp32 VALU, one thread per valid query (key) sweeping all valid keys (queries) serially: the SMALL-T path (64
+// tokens at the 8x8 level, 256 at the default denoiser's 16x16 level, valid extents off the tile grid), where a step is bound by its
+// launches rather than by these FLOPs.  Long token grids (1024 / 4096 tokens of the 256x256 configuration) take
+// dmd_attention_bwd_mfma further down; grad_ops.attention_bwd chooses by the valid token count (ATTN_BWD_MFMA_MIN_T).
 //   rows kernel: one thread per query row i -- softmax statistics (m_i, l_i) by a first sweep over the keys, then dq_i;
-//                writes (m_i, l_i, D_i) for the second kernel;
+//                writes (m_i, l_i, D_i) for the second kernel, indexed by the valid token; its workgroups behind the valid ones
+//                (blockIdx.x >= nbv) write the dqkv rows outside the extent as zero;
 //   cols kernel: one thread per key row j -- dk_j, dv_j by a sweep over the queries.
-// d == 8.  qkv / dqkv are NHWC (N, T, 3C): q | k | v channel thirds, head h = channels [8h, 8h + 8).
+// Thread li <-> valid token (li / vw, li % vw); the sweeps walk the valid rows and columns in token order, so every way of writing
+// the same tokens -- (H, W, H, W), or dmd_attention_bwd's (1, T, 1, T), one outer iteration and a flat sweep -- forms every sum in
+// the same order (bitwise the same result).  Nothing outside the extent is read (the margins of qkv / y / dy are unspecified, NaN
+// included).
 // ------------------------------------------------------------------------------------------------
 struct f8 {
   float v[8];
@@ -439,116 +470,13 @@ __device__ __forceinline__ float dot8(const f8& a, const f8& b) {
 
 __global__ __launch_bounds__(64) void attention_bwd_rows_kernel(const float* __restrict__ qkv, const float* __restrict__ y,
                                                                 const float* __restrict__ dy, float* __restrict__ dqkv,
-                                                                float* __restrict__ rowstat, int T, int C) {
-  const int i = blockIdx.x * 64 + threadIdx.x, h = blockIdx.y, n = blockIdx.z, H = C / 8;
-  if (i >= T) return;
-  const float scale = 0.35355339059327373f;  // 1 / sqrt(8)
-  const size_t row = ((size_t)n * T + i);
-  const f8 q = ld8(qkv + row * 3 * C + h * 8);
-  const f8 yo = ld8(y + row * C + h * 8), dyo = ld8(dy + row * C + h * 8);
-  const float D = dot8(dyo, yo);
-  const float* kbase = qkv + (size_t)n * T * 3 * C + C + h * 8;
-  const float* vbase = kbase + C;
-  float m = -INFINITY, l = 0.f;
-  for (int j = 0; j < T; ++j) {
-    const float s = dot8(q, ld8(kbase + (size_t)j * 3 * C)) * scale;
-    const float mn = fmaxf(m, s);
-    l = l * expf(m - mn) + expf(s - mn);
-    m = mn;
-  }
-  f8 dq;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) dq.v[e] = 0.f;
-  for (int j = 0; j < T; ++j) {
-    const f8 k = ld8(kbase + (size_t)j * 3 * C);
-    const float s = dot8(q, k) * scale;
-    const float p = expf(s - m) / l;
-    const float ds = p * (dot8(dyo, ld8(vbase + (size_t)j * 3 * C)) - D);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) dq.v[e] = __builtin_fmaf(ds * scale, k.v[e], dq.v[e]);
-  }
-  float* o = dqkv + row * 3 * C + h * 8;
-  *(f32x4*)o = (f32x4){dq.v[0], dq.v[1], dq.v[2], dq.v[3]};
-  *(f32x4*)(o + 4) = (f32x4){dq.v[4], dq.v[5], dq.v[6], dq.v[7]};
-  float* rs = rowstat + (((size_t)n * H + h) * T + i) * 4;
-  rs[0] = m;
-  rs[1] = l;
-  rs[2] = D;
-}
-
-__global__ __launch_bounds__(64) void attention_bwd_cols_kernel(const float* __restrict__ qkv, const float* __restrict__ dy,
-                                                                const float* __restrict__ rowstat, float* __restrict__ dqkv, int T,
-                                                                int C) {
-  const int j = blockIdx.x * 64 + threadIdx.x, h = blockIdx.y, n = blockIdx.z, H = C / 8;
-  if (j >= T) return;
-  const float scale = 0.35355339059327373f;
-  const size_t row = ((size_t)n * T + j);
-  const f8 k = ld8(qkv + row * 3 * C + C + h * 8), v = ld8(qkv + row * 3 * C + 2 * C + h * 8);
-  const float* qbase = qkv + (size_t)n * T * 3 * C + h * 8;
-  const float* dybase = dy + (size_t)n * T * C + h * 8;
-  const float* rs = rowstat + ((size_t)n * H + h) * T * 4;
-  f8 dk, dv;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) dk.v[e] = dv.v[e] = 0.f;
-  for (int i = 0; i < T; ++i) {
-    const f8 q = ld8(qbase + (size_t)i * 3 * C);
-    const f8 dyo = ld8(dybase + (size_t)i * C);
-    const float s = dot8(q, k) * scale;
-    const float p = expf(s - rs[4 * i]) / rs[4 * i + 1];
-    const float ds = p * (dot8(dyo, v) - rs[4 * i + 2]);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      dk.v[e] = __builtin_fmaf(ds * scale, q.v[e], dk.v[e]);
-      dv.v[e] = __builtin_fmaf(p, dyo.v[e], dv.v[e]);
-    }
-  }
-  float* o = dqkv + row * 3 * C + C + h * 8;
-  *(f32x4*)o = (f32x4){dk.v[0], dk.v[1], dk.v[2], dk.v[3]};
-  *(f32x4*)(o + 4) = (f32x4){dk.v[4], dk.v[5], dk.v[6], dk.v[7]};
-  o += C;
-  *(f32x4*)o = (f32x4){dv.v[0], dv.v[1], dv.v[2], dv.v[3]};
-  *(f32x4*)(o + 4) = (f32x4){dv.v[4], dv.v[5], dv.v[6], dv.v[7]};
-}
-
-extern "C" int64_t dmd_attention_bwd_workspace_floats(int N, int T, int C) { return (int64_t)N * (C / 8) * T * 4; }
-
-extern "C" int dmd_attention_bwd(const float* qkv, const float* y, const float* dy, float* dqkv, float* workspace, int N, int T,
-                                 int C, int head_dim, dmd_stream_t stream) {
-  DMD_CHECK_ARG(qkv && y && dy && dqkv && workspace, "attention_bwd: null");
-  DMD_CHECK_ARG(head_dim == 8 && C % 8 == 0 && N > 0 && T > 0, "attention_bwd: head_dim must be 8 (got %d), C %% 8 == 0", head_dim);
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid((T + 63) / 64, C / 8, N);
-  hipLaunchKernelGGL(attention_bwd_rows_kernel, grid, dim3(64), 0, st, qkv, y, dy, dqkv, workspace, T, C);
-  hipLaunchKernelGGL(attention_bwd_cols_kernel, grid, dim3(64), 0, st, qkv, dy, (const float*)workspace, dqkv, T, C);
-  DMD_LAUNCH_CHECK();
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// dmd_attention_bwd_valid -- the gradient of dmd_attention_valid: the same two kernels over the (vh, vw) part of an (H, W) token
-// grid (dmd_conv_params: VALID EXTENT).  Thread li <-> valid token (li / vw, li % vw); the sweeps walk the valid rows and columns
-// in token order, so with (vh, vw) == (H, W) every sum is formed as in dmd_attention_bwd (bitwise the same result).  Nothing
-// outside the extent is read (the margins of qkv / y / dy are unspecified, NaN included); the rows kernel's workgroups behind the
-// valid ones write the dqkv rows outside the extent as zero.  rowstat is indexed by the valid token.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void attention_bwd_valid_rows_kernel(const float* __restrict__ qkv, const float* __restrict__ y,
-                                                                      const float* __restrict__ dy, float* __restrict__ dqkv,
-                                                                      float* __restrict__ rowstat, int T, int W, int vh, int vw,
-                                                                      int C, int nbv) {
+                                                                float* __restrict__ rowstat, int T, int W, int vh, int vw, int C,
+                                                                int nbv) {
   const int h = blockIdx.y, n = blockIdx.z, NH = C / 8, V = vh * vw;
   if ((int)blockIdx.x >= nbv) {
-    // the m-th token outside the extent: rows < vh, columns >= vw first, then the rows >= vh
-    const int m = ((int)blockIdx.x - nbv) * 64 + threadIdx.x, side = vh * (W - vw);
+    const int m = ((int)blockIdx.x - nbv) * 64 + threadIdx.x;
     if (m >= T - V) return;
-    int r, c;
-    if (m < side) {
-      r = m / (W - vw);
-      c = vw + (m - r * (W - vw));
-    } else {
-      r = vh + (m - side) / W;
-      c = (m - side) - (r - vh) * W;
-    }
-    float* o = dqkv + ((size_t)n * T + (size_t)r * W + c) * 3 * C + h * 8;
+    float* o = dqkv + ((size_t)n * T + ab_margin_token(m, W, vh, vw)) * 3 * C + h * 8;
     const f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
@@ -559,7 +487,7 @@ __global__ __launch_bounds__(64) void attention_bwd_valid_rows_kernel(const floa
   }
   const int li = blockIdx.x * 64 + threadIdx.x;
   if (li >= V) return;
-  const int qr = li / vw, i = qr * W + (li - qr * vw);
+  const int i = ab_token(li, W, vw);
   const float scale = 0.35355339059327373f;  // 1 / sqrt(8)
   const size_t row = ((size_t)n * T + i);
   const f8 q = ld8(qkv + row * 3 * C + h * 8);
@@ -601,12 +529,12 @@ __global__ __launch_bounds__(64) void attention_bwd_valid_rows_kernel(const floa
   rs[2] = D;
 }
 
-__global__ __launch_bounds__(64) void attention_bwd_valid_cols_kernel(const float* __restrict__ qkv, const float* __restrict__ dy,
-                                                                      const float* __restrict__ rowstat, float* __restrict__ dqkv,
-                                                                      int T, int W, int vh, int vw, int C) {
+__global__ __launch_bounds__(64) void attention_bwd_cols_kernel(const float* __restrict__ qkv, const float* __restrict__ dy,
+                                                                const float* __restrict__ rowstat, float* __restrict__ dqkv, int T,
+                                                                int W, int vh, int vw, int C) {
   const int lj = blockIdx.x * 64 + threadIdx.x, h = blockIdx.y, n = blockIdx.z, NH = C / 8, V = vh * vw;
   if (lj >= V) return;
-  const int kr = lj / vw, j = kr * W + (lj - kr * vw);
+  const int j = ab_token(lj, W, vw);
   const float scale = 0.35355339059327373f;
   const size_t row = ((size_t)n * T + j);
   const f8 k = ld8(qkv + row * 3 * C + C + h * 8), v = ld8(qkv + row * 3 * C + 2 * C + h * 8);
@@ -641,22 +569,33 @@ __global__ __launch_bounds__(64) void attention_bwd_valid_cols_kernel(const floa
   *(f32x4*)(o + 4) = (f32x4){dv.v[4], dv.v[5], dv.v[6], dv.v[7]};
 }
 
-extern "C" int dmd_attention_bwd_valid(const float* qkv, const float* y, const float* dy, float* dqkv, float* workspace, int N, int H,
-                                       int W, int valid_h, int valid_w, int C, int head_dim, dmd_stream_t stream) {
-  DMD_CHECK_ARG(qkv && y && dy && dqkv && workspace, "attention_bwd_valid: null");
-  DMD_CHECK_ARG(head_dim == 8 && C % 8 == 0 && N > 0 && H > 0 && W > 0,
-                "attention_bwd_valid: head_dim must be 8 (got %d), C %% 8 == 0 (C=%d), N, H, W > 0", head_dim, C);
-  DMD_CHECK_ARG(valid_h > 0 && valid_h <= H && valid_w > 0 && valid_w <= W, "attention_bwd_valid: valid extent %d x %d of %d x %d",
-                valid_h, valid_w, H, W);
-  hipStream_t st = (hipStream_t)stream;
-  const int T = H * W, V = valid_h * valid_w;
+extern "C" int64_t dmd_attention_bwd_workspace_floats(int N, int T, int C) { return (int64_t)N * (C / 8) * T * 4; }
+
+// the scalar pair over the (vh, vw) extent of an (H, W) grid; vw == W, vh == H: no margin workgroup (nbm == 0)
+static int att_bwd_scalar(const float* qkv, const float* y, const float* dy, float* dqkv, float* workspace, int N, int H, int W, int vh,
+                          int vw, int C, hipStream_t st) {
+  const int T = H * W, V = vh * vw;
   const int nbv = (V + 63) / 64, nbm = (T - V + 63) / 64;
-  hipLaunchKernelGGL(attention_bwd_valid_rows_kernel, dim3(nbv + nbm, C / 8, N), dim3(64), 0, st, qkv, y, dy, dqkv, workspace, T, W,
-                     valid_h, valid_w, C, nbv);
-  hipLaunchKernelGGL(attention_bwd_valid_cols_kernel, dim3(nbv, C / 8, N), dim3(64), 0, st, qkv, dy, (const float*)workspace, dqkv, T,
-                     W, valid_h, valid_w, C);
+  hipLaunchKernelGGL(attention_bwd_rows_kernel, dim3(nbv + nbm, C / 8, N), dim3(64), 0, st, qkv, y, dy, dqkv, workspace, T, W, vh, vw, C,
+                     nbv);
+  hipLaunchKernelGGL(attention_bwd_cols_kernel, dim3(nbv, C / 8, N), dim3(64), 0, st, qkv, dy, (const float*)workspace, dqkv, T, W, vh,
+                     vw, C);
   DMD_LAUNCH_CHECK();
   return 0;
+}
+
+// any T > 0: the whole grid is the extent (1, T, 1, T) of a (1, T) grid
+extern "C" int dmd_attention_bwd(const float* qkv, const float* y, const float* dy, float* dqkv, float* workspace, int N, int T,
+                                 int C, int head_dim, dmd_stream_t stream) {
+  if (att_check_args("attention_bwd", qkv && y && dy && dqkv && workspace, N, 1, T, 1, T, C, head_dim)) return 1;
+  return att_bwd_scalar(qkv, y, dy, dqkv, workspace, N, 1, T, 1, T, C, (hipStream_t)stream);
+}
+
+// the gradient of dmd_attention_valid; the dqkv rows outside the extent are written as zero
+extern "C" int dmd_attention_bwd_valid(const float* qkv, const float* y, const float* dy, float* dqkv, float* workspace, int N, int H,
+                                       int W, int valid_h, int valid_w, int C, int head_dim, dmd_stream_t stream) {
+  if (att_check_args("attention_bwd_valid", qkv && y && dy && dqkv && workspace, N, H, W, valid_h, valid_w, C, head_dim)) return 1;
+  return att_bwd_scalar(qkv, y, dy, dqkv, workspace, N, H, W, valid_h, valid_w, C, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -685,11 +624,6 @@ extern "C" int dmd_attention_bwd_valid(const float* qkv, const float* y, const f
 #define AB_EXP_SCALE 0.51006973f  // log2(e) / sqrt(8)
 #define AB_SCALE 0.35355339059327373f
 
-__device__ __forceinline__ int ab_token(int li, int W, int vw) {
-  const int r = li / vw;
-  return r * W + (li - r * vw);
-}
-
 struct AbKeyTile {
   float k[AB_KT][8];
   float v[AB_KT][8];
@@ -715,18 +649,9 @@ __global__ __launch_bounds__(256) void attention_bwd_mfma_q_kernel(const float* 
   const size_t row = (size_t)3 * C;
   const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
   if ((int)blockIdx.x >= nbv) {
-    // the m-th token outside the extent: rows < vh, columns >= vw first, then the rows >= vh
-    const int m = ((int)blockIdx.x - nbv) * 256 + tid, side = vh * (W - vw);
+    const int m = ((int)blockIdx.x - nbv) * 256 + tid;
     if (m >= T - V) return;
-    int r, c;
-    if (m < side) {
-      r = m / (W - vw);
-      c = vw + (m - r * (W - vw));
-    } else {
-      r = vh + (m - side) / W;
-      c = (m - side) - (r - vh) * W;
-    }
-    float* o = dqkv + ((size_t)n * T + (size_t)r * W + c) * row + h * 8;
+    float* o = dqkv + ((size_t)n * T + ab_margin_token(m, W, vh, vw)) * row + h * 8;
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
       *(f32x4*)(o + t * C) = zero4;
@@ -940,11 +865,7 @@ __global__ __launch_bounds__(256) void attention_bwd_mfma_k_kernel(const float* 
 
 extern "C" int dmd_attention_bwd_mfma(const float* qkv, const float* y, const float* dy, float* dqkv, float* workspace, int N, int H,
                                       int W, int valid_h, int valid_w, int C, int head_dim, dmd_stream_t stream) {
-  DMD_CHECK_ARG(qkv && y && dy && dqkv && workspace, "attention_bwd_mfma: null");
-  DMD_CHECK_ARG(head_dim == 8 && C % 8 == 0 && N > 0 && H > 0 && W > 0,
-                "attention_bwd_mfma: head_dim must be 8 (got %d), C %% 8 == 0 (C=%d), N, H, W > 0", head_dim, C);
-  DMD_CHECK_ARG(valid_h > 0 && valid_h <= H && valid_w > 0 && valid_w <= W, "attention_bwd_mfma: valid extent %d x %d of %d x %d",
-                valid_h, valid_w, H, W);
+  if (att_check_args("attention_bwd_mfma", qkv && y && dy && dqkv && workspace, N, H, W, valid_h, valid_w, C, head_dim)) return 1;
   hipStream_t st = (hipStream_t)stream;
   const int T = H * W, V = valid_h * valid_w;
   const int nbv = (V + 63) / 64, nbm = (T - V + 255) / 256;
@@ -996,18 +917,9 @@ __global__ __launch_bounds__(256) void attention_f32_tiled_kernel(const float* _
   const size_t row = (size_t)3 * C;
   const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
   if ((int)blockIdx.x >= nbv) {
-    // the m-th token outside the extent: rows < vh, columns >= vw first, then the rows >= vh
-    const int m = ((int)blockIdx.x - nbv) * 256 + tid, side = vh * (W - vw);
+    const int m = ((int)blockIdx.x - nbv) * 256 + tid;
     if (m >= T - V) return;
-    int r, c;
-    if (m < side) {
-      r = m / (W - vw);
-      c = vw + (m - r * (W - vw));
-    } else {
-      r = vh + (m - side) / W;
-      c = (m - side) - (r - vh) * W;
-    }
-    float* o = out + ((size_t)n * T + (size_t)r * W + c) * C + h * 8;
+    float* o = out + ((size_t)n * T + ab_margin_token(m, W, vh, vw)) * C + h * 8;
     *(f32x4*)o = zero4;
     *(f32x4*)(o + 4) = zero4;
     return;
@@ -1154,11 +1066,7 @@ __global__ __launch_bounds__(256) void attention_f32_tiled_kernel(const float* _
 
 extern "C" int dmd_attention_f32(const float* qkv, float* out, int N, int H, int W, int valid_h, int valid_w, int C, int head_dim,
                                  dmd_stream_t stream) {
-  DMD_CHECK_ARG(qkv && out, "attention_f32: null");
-  DMD_CHECK_ARG(head_dim == 8, "attention_f32: head_dim must be 8 (ATTN_HEAD_DIM), got %d", head_dim);
-  DMD_CHECK_ARG(C % 8 == 0 && C > 0 && N > 0 && H > 0 && W > 0, "attention_f32: need C %% 8 == 0, N, H, W > 0 (H=%d W=%d C=%d)", H, W, C);
-  DMD_CHECK_ARG(valid_h > 0 && valid_h <= H && valid_w > 0 && valid_w <= W, "attention_f32: valid extent %d x %d of %d x %d", valid_h,
-                valid_w, H, W);
+  if (att_check_args("attention_f32", qkv && out, N, H, W, valid_h, valid_w, C, head_dim)) return 1;
   const int T = H * W, V = valid_h * valid_w;
   const int nbv = (V + 64 * AT_QG - 1) / (64 * AT_QG), nbm = (T - V + 255) / 256;
   hipLaunchKernelGGL(attention_f32_tiled_kernel, dim3(nbv + nbm, C / 8, N), dim3(256), 0, (hipStream_t)stream, qkv, out, T, W, valid_h,

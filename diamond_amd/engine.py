@@ -51,6 +51,10 @@ class AttnRecord:
     head_dim: int
     valid: Optional[Tuple[int, int]] = None  # the token grid's VALID EXTENT (dmd_attention_valid), None: all of it
 
+    @property
+    def extent(self) -> Tuple[int, int, int, int]:
+        return token_extent(self.qkv.shape, self.valid)
+
 
 @dataclass
 class CatRecord:
@@ -854,22 +858,12 @@ def attn_f32_tiled_min_t() -> int:
     return ATTN_F32_TILED_MIN_T if v is None or v == "" else int(v)
 
 
-def _attention_f32(qkv: Act, out: Tensor, c: int, head_dim: int) -> None:
-    """the exact-fp32 routes of `attention`"""
-    n, h, w, _ = qkv.shape
-    vh, vw = qkv.valid if qkv.valid is not None else (1, h * w)
-    tv = vh * vw
-    min_t = attn_f32_tiled_min_t()
-    if min_t > 0 and tv >= min_t:  # long token grids: the tiled two-pass kernel, tokens addressed by their valid index
-        gh, gw = (h, w) if qkv.valid is not None else (1, h * w)
-        if nv.PROFILER is not None:  # QK^T and PV over the valid tokens: 2 x (2 T^2 d) per head
-            nv.PROFILER.annotate("attention_f32_tiled_kernel", 4.0 * n * tv * tv * c, 4.0 * n * tv * 4 * c)
-        nv.check(nv.lib().dmd_attention_f32(nv.fptr(qkv.t), nv.fptr(out), n, gh, gw, vh, vw, c, head_dim, nv.stream()), "dmd_attention_f32")
-        return
-    vh, vw = qkv.valid if qkv.valid is not None else (h, w)
-    if nv.PROFILER is not None:
-        nv.PROFILER.annotate("attention_kernel", 4.0 * n * (vh * vw) * (h * w) * c, 4.0 * n * h * w * 4 * c)
-    nv.check(nv.lib().dmd_attention_valid(nv.fptr(qkv.t), nv.fptr(out), n, h, w, vh, vw, c, head_dim, nv.stream()), "dmd_attention_valid")
+def token_extent(shape, valid: Optional[Tuple[int, int]]) -> Tuple[int, int, int, int]:
+    """(gh, gw, vh, vw): the tokens of an (N, H, W, C) activation as the (vh, vw) VALID EXTENT of a row-major (gh, gw) grid -- the
+    kernels' convention (csrc/dmd_attention.hip); with no valid extent the whole grid of T = H W tokens is the extent (1, T) of a
+    (1, T) grid"""
+    _, h, w, _ = shape
+    return (h, w, *valid) if valid is not None else (1, h * w, 1, h * w)
 
 
 def attention(qkv: Act, c: int, head_dim: int = 8, precision: Optional[str] = None) -> Tensor:
@@ -877,23 +871,25 @@ def attention(qkv: Act, c: int, head_dim: int = 8, precision: Optional[str] = No
     n, h, w, c3 = qkv.shape
     assert c3 == 3 * c
     out = torch.empty(n, h, w, c, device=qkv.t.device, dtype=torch.float32)
-    if attn_precision(precision) == "f32":
-        _attention_f32(qkv, out, c, head_dim)
-        if TAPE is not None:
-            TAPE.append(AttnRecord(qkv, out, c, head_dim, qkv.valid))
-        return out
-    if qkv.valid is not None:  # keys outside the valid extent stay out of the softmax
-        nv.check(nv.lib().dmd_attention_valid(nv.fptr(qkv.t), nv.fptr(out), n, h, w, qkv.valid[0], qkv.valid[1], c, head_dim, nv.stream()),
-                 "dmd_attention_valid")
-        if TAPE is not None:
-            TAPE.append(AttnRecord(qkv, out, c, head_dim, qkv.valid))
-        return out
-    if nv.PROFILER is not None:  # QK^T and PV: 2 x (2 T^2 d) per head
-        t = h * w
-        nv.PROFILER.annotate("attention_f16x2_kernel" if t % 256 == 0 else "attention_kernel", 4.0 * n * t * t * c, 4.0 * n * t * 4 * c)
-    nv.check(nv.lib().dmd_attention(nv.fptr(qkv.t), nv.fptr(out), n, h * w, c, head_dim, nv.stream()), "dmd_attention")
+    t = h * w
+    gh, gw, vh, vw = token_extent(qkv.shape, qkv.valid)
+    tv = vh * vw
+    exact = attn_precision(precision) == "f32"
+    # (key, FLOPs, bytes) of the launch for the profiler -- QK^T and PV: 2 x (2 T^2 d) per head -- or None
+    if exact and 0 < attn_f32_tiled_min_t() <= tv:  # long token grids: the tiled two-pass kernel, over the valid tokens only
+        note = ("attention_f32_tiled_kernel", 4.0 * n * tv * tv * c, 4.0 * n * tv * 4 * c)
+        name, args = "dmd_attention_f32", (n, gh, gw, vh, vw, c)
+    elif exact or qkv.valid is not None:  # attention_kernel over the padded grid; keys outside the valid extent stay out of the softmax
+        note = ("attention_kernel", 4.0 * n * tv * t * c, 4.0 * n * t * 4 * c) if exact else None
+        name, args = "dmd_attention_valid", (n, h, w, *(qkv.valid or (h, w)), c)
+    else:  # dmd_attention's routing by T alone
+        note = ("attention_f16x2_kernel" if t % 256 == 0 else "attention_kernel", 4.0 * n * t * t * c, 4.0 * n * t * 4 * c)
+        name, args = "dmd_attention", (n, t, c)
+    if note is not None and nv.PROFILER is not None:
+        nv.PROFILER.annotate(*note)
+    nv.check(getattr(nv.lib(), name)(nv.fptr(qkv.t), nv.fptr(out), *args, head_dim, nv.stream()), name)
     if TAPE is not None:
-        TAPE.append(AttnRecord(qkv, out, c, head_dim))
+        TAPE.append(AttnRecord(qkv, out, c, head_dim, qkv.valid))
     return out
 
 

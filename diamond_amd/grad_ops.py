@@ -7,6 +7,7 @@ backward of the U-Net and the reward / end encoder (unet_train.py):
   dgrad_weights   the packed weights of the data gradient, which is dmd_conv2d (engine.conv2d) on the flipped / transposed weight
   gn_bwd          dmd_gn_silu_bwd (GroupNorm + FiLM / affine + SiLU or identity)
   pow2_scaled     the 2^k scaling both backward passes run under
+  attention_bwd   dmd_attention_bwd / _bwd_valid (one scalar pair of kernels) or, for long token grids, dmd_attention_bwd_mfma
   rew_end_loss    dmd_rew_end_loss (the reward / end model's two cross-entropies, their gradient and confusion matrices: one launch)
 
 Plumbing only, like engine.py; the arithmetic ("f16x2" / "f32") is its callers' choice and arrives as an argument.
@@ -22,7 +23,18 @@ from torch import Tensor, nn
 
 from . import engine as E
 from . import native as nv
-from .engine import Act, NormSpec
+from .engine import Act, AttnRecord, NormSpec
+
+# Attention backward: from this many VALID tokens on, the tiled fp32-MFMA kernels (dmd_attention_bwd_mfma) instead of the one-thread-
+# per-token pair.  Measured (profiles/attention_bwd_mfma.json); the 256 .. 1023 token range stays on the scalar pair, whose launch
+# sequence and bits the default 64x64 step is pinned to.  DIAMOND_ATTN_BWD_MIN_T=n overrides it (read at every backward), 0 = never.
+# (Both names are re-exported by unet_train.)
+ATTN_BWD_MFMA_MIN_T = 1024
+
+
+def attn_bwd_mfma_min_t() -> int:
+    v = os.environ.get("DIAMOND_ATTN_BWD_MIN_T")
+    return ATTN_BWD_MFMA_MIN_T if v is None or v == "" else int(v)
 
 
 def pow2_scaled(d: Tensor) -> Tuple[Tensor, Tensor]:
@@ -277,6 +289,27 @@ def gn_bwd(x: Act, spec: NormSpec, da: Tensor, dskip: Optional[Tensor], identity
         nv.PROFILER.annotate("dmd_gn_silu_bwd", 0.0, 4.0 * x.t.numel() * (3 + (dskip is not None)))
     nv.check(nv.lib().dmd_gn_silu_bwd(C.byref(p), nv.stream()), "dmd_gn_silu_bwd")
     return dx, dma
+
+
+def attention_bwd(rec: AttnRecord, dy: Tensor) -> Tensor:
+    """dqkv of a recorded attention launch from dy, the gradient of its output; zero outside the valid extent"""
+    n, h, w, _ = rec.qkv.shape
+    gh, gw, vh, vw = rec.extent
+    dqkv = torch.empty_like(rec.qkv.t)
+    ws = torch.empty(int(nv.lib().dmd_attention_bwd_workspace_floats(n, h * w, rec.c)), device=dy.device, dtype=torch.float32)
+    dyc = dy.contiguous()
+    ptrs = (nv.fptr(rec.qkv.t), nv.fptr(rec.out), nv.fptr(dyc), nv.fptr(dqkv), nv.fptr(ws))
+    if 0 < attn_bwd_mfma_min_t() <= vh * vw:  # long token grids: tiled fp32 MFMA kernels
+        nv.check_current_device(dy.device)
+        if nv.PROFILER is not None:  # 7 contractions of 8 MACs per (query, key) pair and head
+            nv.PROFILER.annotate("dmd_attention_bwd_mfma", 14.0 * n * (vh * vw) ** 2 * rec.c, 4.0 * n * vh * vw * 8 * rec.c)
+        name, args = "dmd_attention_bwd_mfma", (n, gh, gw, vh, vw)
+    elif rec.valid is not None:  # queries and keys of the valid extent only
+        name, args = "dmd_attention_bwd_valid", (n, gh, gw, vh, vw)
+    else:  # the same pair of kernels over the whole grid
+        name, args = "dmd_attention_bwd", (n, h * w)
+    nv.check(getattr(nv.lib(), name)(*ptrs, *args, rec.c, rec.head_dim, nv.stream()), name)
+    return dqkv
 
 
 class RewEndLossFn(torch.autograd.Function):

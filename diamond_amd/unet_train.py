@@ -15,7 +15,7 @@ Per recorded convolution, with dOut the gradient of its output (the launches the
     (AdaGroupNorm) or the affine parameters of an nn.GroupNorm;
   * residual                -> accumulated into the gradient of the residual tensor (through the GroupNorm affine for
     the attention block's `x_normed + out_proj(y)`, blocks.py:72).
-Attention core: `dmd_attention_bwd`, from ATTN_BWD_MFMA_MIN_T valid tokens on `dmd_attention_bwd_mfma` (fp32 matrix cores).
+Attention core: grad_ops.attention_bwd (`dmd_attention_bwd`, from ATTN_BWD_MFMA_MIN_T valid tokens on `dmd_attention_bwd_mfma`).
 The FiLM table itself (`cond @ W_cat^T + b_cat`), the 256-wide cond MLP and the
 action embedding are a handful of tiny GEMMs: they run as torch ops under ordinary autograd, so the table gradient
 returned here flows on into the 44 AdaGroupNorm linears, `cond_proj` and `act_emb`.
@@ -25,7 +25,6 @@ weight gradients / GroupNorm backward: their source's, attention: `dmd_attention
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -35,17 +34,9 @@ from . import engine as E
 from . import grad_ops as G
 from . import native as nv
 from .engine import Act, AttnRecord, CatRecord, ConvRecord, NormSpec
+from .grad_ops import ATTN_BWD_MFMA_MIN_T, attn_bwd_mfma_min_t  # noqa: F401  (read-only here: tools and tests read the default; DIAMOND_ATTN_BWD_MIN_T overrides it)
 
 TRAIN_PRECISION = "f16x2"  # arithmetic of the forward, dgrad and wgrad convolutions (split-fp16 operands, fp32 accumulate); "f32" = exact
-# Attention backward: from this many VALID tokens on, the tiled fp32-MFMA kernels (dmd_attention_bwd_mfma) instead of the one-thread-
-# per-token pair.  Measured (profiles/attention_bwd_mfma.json); the 256 .. 1023 token range stays on the scalar pair, whose launch
-# sequence and bits the default 64x64 step is pinned to.  DIAMOND_ATTN_BWD_MIN_T=n overrides it (read at every backward), 0 = never.
-ATTN_BWD_MFMA_MIN_T = 1024
-
-
-def attn_bwd_mfma_min_t() -> int:
-    v = os.environ.get("DIAMOND_ATTN_BWD_MIN_T")
-    return ATTN_BWD_MFMA_MIN_T if v is None or v == "" else int(v)
 
 
 def _key(t: Tensor) -> int:
@@ -159,28 +150,7 @@ def backward_tape(tape: List, cache: E.PackCache, d_out: Tensor, table: Tensor, 
             dy = grads.pop(rec.out)
             if dy is None:
                 continue
-            n, h, w, c3 = rec.qkv.shape
-            dqkv = torch.empty_like(rec.qkv.t)
-            ws = torch.empty(int(nv.lib().dmd_attention_bwd_workspace_floats(n, h * w, rec.c)), device=dy.device,
-                             dtype=torch.float32)
-            dyc = dy.contiguous()
-            vh, vw = rec.valid if rec.valid is not None else (1, h * w)
-            min_t = attn_bwd_mfma_min_t()
-            if min_t > 0 and vh * vw >= min_t:  # long token grids: tiled fp32 MFMA kernels, the same extent convention
-                nv.check_current_device(dy.device)
-                gh, gw = (h, w) if rec.valid is not None else (1, h * w)
-                if nv.PROFILER is not None:  # 7 contractions of 8 MACs per (query, key) pair and head
-                    nv.PROFILER.annotate("dmd_attention_bwd_mfma", 14.0 * n * (vh * vw) ** 2 * rec.c, 4.0 * n * vh * vw * 8 * rec.c)
-                nv.check(nv.lib().dmd_attention_bwd_mfma(nv.fptr(rec.qkv.t), nv.fptr(rec.out), nv.fptr(dyc), nv.fptr(dqkv), nv.fptr(ws),
-                                                         n, gh, gw, vh, vw, rec.c, rec.head_dim, nv.stream()), "dmd_attention_bwd_mfma")
-            elif rec.valid is not None:  # queries and keys of the valid extent only; dqkv zero outside it
-                nv.check(nv.lib().dmd_attention_bwd_valid(nv.fptr(rec.qkv.t), nv.fptr(rec.out), nv.fptr(dyc), nv.fptr(dqkv), nv.fptr(ws),
-                                                          n, h, w, rec.valid[0], rec.valid[1], rec.c, rec.head_dim, nv.stream()),
-                         "dmd_attention_bwd_valid")
-            else:
-                nv.check(nv.lib().dmd_attention_bwd(nv.fptr(rec.qkv.t), nv.fptr(rec.out), nv.fptr(dyc), nv.fptr(dqkv),
-                                                    nv.fptr(ws), n, h * w, rec.c, rec.head_dim, nv.stream()), "dmd_attention_bwd")
-            grads.add(rec.qkv.t, dqkv)
+            grads.add(rec.qkv.t, G.attention_bwd(rec, dy))
             continue
         if isinstance(rec, CatRecord):  # a materialised channel concatenation (engine.concat): the gradient split by channels
             dy = grads.pop(rec.out.t)

@@ -237,15 +237,18 @@ int dmd_attention_valid(const float* qkv, float* out, int N, int H, int W, int v
 int dmd_attention_f32(const float* qkv, float* out, int N, int H, int W, int valid_h, int valid_w, int C, int head_dim,
                       dmd_stream_t stream);
 /* Backward of dmd_attention (autograd of blocks.py:66-71 under the denoiser training loss, denoiser.py:93-122):
- * y = the forward's output, dy its gradient -> dqkv (N, T, 3C) in the qkv layout.  workspace: dmd_attention_bwd_workspace_floats. */
+ * y = the forward's output, dy its gradient -> dqkv (N, T, 3C) in the qkv layout.  workspace: dmd_attention_bwd_workspace_floats.
+ * Any T > 0.  dmd_attention_bwd and dmd_attention_bwd_valid launch ONE pair of scalar kernels (attention_bwd_rows_kernel,
+ * attention_bwd_cols_kernel, one thread per valid token): the whole grid of T tokens is the extent (1, T, 1, T) of a (1, T) grid. */
 int64_t dmd_attention_bwd_workspace_floats(int N, int T, int C);
 int dmd_attention_bwd(const float* qkv, const float* y, const float* dy, float* dqkv, float* workspace, int N, int T, int C,
                       int head_dim, dmd_stream_t stream);
 /* (ABI v11 addition) Backward of dmd_attention_valid over the (valid_h, valid_w) part of an (H, W) token grid (dmd_conv_params:
  * VALID EXTENT): only tokens with row < valid_h and column < valid_w take part, as queries and as keys, and nothing outside the
  * extent is read -- the margins of qkv, y and dy may hold anything, NaN / Inf included.  The dqkv rows outside the extent are
- * written as ZERO in all three thirds.  The work is sized by the valid token count; with (valid_h, valid_w) == (H, W) the result
- * is bitwise dmd_attention_bwd's (same summation order).  workspace: dmd_attention_bwd_workspace_floats(N, H * W, C). */
+ * written as ZERO in all three thirds.  The work is sized by the valid token count; every way of writing the same
+ * tokens -- (H, W, H, W), (1, H W, 1, H W), dmd_attention_bwd(N, H W) -- gives bitwise the same result (same kernels, same summation
+ * order).  workspace: dmd_attention_bwd_workspace_floats(N, H * W, C). */
 int dmd_attention_bwd_valid(const float* qkv, const float* y, const float* dy, float* dqkv, float* workspace, int N, int H, int W,
                             int valid_h, int valid_w, int C, int head_dim, dmd_stream_t stream);
 /* (ABI v11 addition) The same gradient on the fp32 matrix cores (v_mfma_f32_16x16x4_f32, exact fp32 operands), for long token

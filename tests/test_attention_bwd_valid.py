@@ -1,7 +1,9 @@
 """dmd_attention_bwd_valid: the gradient of dmd_attention_valid over the (valid_h, valid_w) part of an (H, W) token grid, against
 float64 torch autograd of the attention of the CROPPED tensors.  The buffer margins of qkv, y and dy hold huge values and NaN (what
 torch.empty may hand the kernel): none of them may reach a result, and dqkv is exactly zero outside the extent.  With the extent
-the whole grid the result is bitwise dmd_attention_bwd's.  On the SIMT interpreter (CPU) and on the device (-m gpu)."""
+the whole grid the result is bitwise dmd_attention_bwd's, whichever way the whole grid is written: (H, W, H, W) or one row of H W
+tokens, (1, H W, 1, H W), which is how dmd_attention_bwd launches the scalar pair.  On the SIMT interpreter (CPU) and on the device
+(-m gpu)."""
 import numpy as np
 import pytest
 import torch
@@ -10,7 +12,7 @@ CASES = [(16, 16, 9, 9), (16, 16, 9, 10), (32, 32, 18, 20), (64, 64, 36, 36)]
 C, N = 64, 2
 
 
-def make_inputs(h, w, vh, vw, seed):
+def make_inputs(h, w, vh, vw, seed, N=N, C=C):
     """qkv / y / dy (N, H, W, .) float32 with garbage margins, and the float64 reference dqkv of the valid tokens"""
     g = torch.Generator().manual_seed(seed)
     qkv = torch.randn(N, h, w, 3 * C, generator=g, dtype=torch.float64) * 1.5
@@ -42,6 +44,7 @@ def check(dqkv, want, inside, vh, vw):
 
 
 def run_simt(qkv, y, dy, h, w, vh, vw, full=False):
+    N, C = qkv.shape[0], qkv.shape[-1] // 3
     from tests.simt import loader as S
     from tests.simt.fence import fenced as G
 
@@ -58,6 +61,7 @@ def run_simt(qkv, y, dy, h, w, vh, vw, full=False):
 
 
 def run_gpu(qkv, y, dy, h, w, vh, vw, full=False):
+    N, C = qkv.shape[0], qkv.shape[-1] // 3
     from diamond_amd import native as nv
 
     a = [t.cuda().contiguous() for t in (qkv, y, dy)]
@@ -89,6 +93,24 @@ def test_attention_bwd_valid_over_the_whole_grid_is_bitwise_attention_bwd(run, h
     got = run(qkv, y, dy, h, w, h, w)
     check(got, want, inside, h, w)
     assert torch.equal(got, run(qkv, y, dy, h, w, h, w, full=True))
+
+
+@pytest.mark.parametrize("run", RUNNERS.values(), ids=RUNNERS.keys())
+@pytest.mark.parametrize("h,w", [(8, 8), (16, 16)])
+def test_attention_bwd_valid_over_the_whole_grid_as_one_row_of_tokens_is_bitwise_the_same(run, h, w):
+    """(H, W, H, W) against (1, H W, 1, H W): the extent dmd_attention_bwd gives the scalar pair"""
+    qkv, y, dy, want, inside = make_inputs(h, w, h, w, seed=h)
+    got = run(qkv, y, dy, h, w, h, w)
+    check(got, want, inside, h, w)
+    one_row = lambda t: t.reshape(N, 1, h * w, -1)
+    assert torch.equal(one_row(got), run(one_row(qkv), one_row(y), one_row(dy), 1, h * w, 1, h * w))
+
+
+@pytest.mark.parametrize("run", RUNNERS.values(), ids=RUNNERS.keys())
+def test_attention_bwd_with_a_partial_last_workgroup(run):
+    """T = 100: the second workgroup of 64 threads holds 36 tokens"""
+    qkv, y, dy, want, inside = make_inputs(1, 100, 1, 100, seed=100, N=1, C=16)
+    check(run(qkv, y, dy, 1, 100, 1, 100, full=True), want, inside, 1, 100)
 
 
 @pytest.mark.parametrize("run", RUNNERS.values(), ids=RUNNERS.keys())
