@@ -2,10 +2,11 @@
 // blocks.py:14).  qkv / dqkv are NHWC (N, T, 3C): q | k | v channel thirds, head h = channels [8h, 8h + 8).  Precision contracts:
 // include/diamond_hip.h; which entry point the host calls: engine.attention (forward), grad_ops.attention_bwd (backward).
 //   entry point              kernel(s)                                      when
-//   dmd_attention            attention_f16x2_kernel                         T % 256 == 0: split-fp16 operands, two passes over the keys
+//   dmd_attention            attention_f16x2_kernel<false>                  T % 256 == 0: split-fp16 operands, two passes over the keys
 //                            attention_kernel                               any other T % 64 == 0: exact fp32, online softmax
 //   dmd_attention_valid      attention_kernel                               always; keys outside the extent are masked
 //   dmd_attention_f32        attention_f32_tiled_kernel                     always: exact fp32, two passes, over the valid tokens
+//   dmd_attention_f16x2      attention_f16x2_kernel<true>                   always: split-fp16 operands, two passes, over the valid tokens
 //   dmd_attention_bwd        attention_bwd_rows_kernel + _cols_kernel       always: the extent (1, T, 1, T) of a (1, T) grid
 //   dmd_attention_bwd_valid  attention_bwd_rows_kernel + _cols_kernel       always: the extent as given
 //   dmd_attention_bwd_mfma   attention_bwd_mfma_q_kernel + _k_kernel        always: fp32 matrix cores, the extent as given
@@ -216,16 +217,103 @@ __device__ __forceinline__ void af_split8(const f32x4& a, const f32x4& b, att_h8
   }
 }
 
-__global__ __launch_bounds__(256, 2) void attention_f16x2_kernel(const float* __restrict__ qkv, float* __restrict__ out, int T, int C,
-                                                              float qscale) {
+// the scores of the keys behind the tile's nk valid ones become -inf: s0[r] is key kb + r of the tile, s1[r] key kb + 16 + r.  A
+// SELECTION, not arithmetic: those keys are staged as zeros, and 0 against an infinite query is NaN
+__device__ __forceinline__ void af_mask_keys(f32x4& s0, f32x4& s1, int kb, int nk) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    s0[r] = kb + r < nk ? s0[r] : -INFINITY;
+    s1[r] = kb + 16 + r < nk ? s1[r] : -INFINITY;
+  }
+}
+// The two inner loop bodies, 32 keys from k0 of tile `tl`: each is expanded twice in the kernel, plain (MASK = (void)0) and with
+// af_mask_keys on the partial last tile of an extent.  Macros, not lambdas or helpers: either of those changed the on-grid
+// kernel's instruction stream; this way the compiler is given exactly the text it had.
+#define AF_PASS1_BLOCK(MASK)                                                                                          \
+  {                                                                                                                   \
+    const att_h8 ka0 = k_frag(tl, k0), ka1 = k_frag(tl, k0 + 16);                                                     \
+    _Pragma("unroll") for (int g = 0; g < AF_QG; ++g) {                                                               \
+      f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ka0, bq[g], zero4, 0, 0, 0);                                  \
+      f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ka1, bq[g], zero4, 0, 0, 0);                                  \
+      MASK;                                                                                                           \
+      mx[g] = af_max3(af_max3(mx[g], s0[0], s0[1]), af_max3(s0[2], s0[3], s1[0]), af_max3(s1[1], s1[2], s1[3]));      \
+    }                                                                                                                 \
+  }
+/* V^T operand: lane (row i = lane & 15, kg): k-slots 0..3 = keys k0 + 4 kg + (0..3), 4..7 = keys k0 + 16 + 4 kg + (0..3);
+   p = h + l: packed fp16 conversion for h, one mixed-precision fma per element for l = fp16(p - h) */
+#define AF_PASS2_BLOCK(MASK)                                                                                          \
+  {                                                                                                                   \
+    const att_h8 ka0 = k_frag(tl, k0), ka1 = k_frag(tl, k0 + 16);                                                     \
+    const att_h4 va = *(const att_h4*)&tl.vt[j][k0 + 4 * kg], vb = *(const att_h4*)&tl.vt[j][k0 + 16 + 4 * kg];       \
+    const att_h8 vf = (att_h8){va[0], va[1], va[2], va[3], vb[0], vb[1], vb[2], vb[3]};                               \
+    _Pragma("unroll") for (int g = 0; g < AF_QG; ++g) {                                                               \
+      f32x4 s0 = AF_LAB(32) ? negm[g] + oacc[g] : __builtin_amdgcn_mfma_f32_16x16x32_f16(ka0, bq[g], negm[g], 0, 0, 0); \
+      f32x4 s1 = AF_LAB(32) ? negm[g] - oacc[g] : __builtin_amdgcn_mfma_f32_16x16x32_f16(ka1, bq[g], negm[g], 0, 0, 0); \
+      MASK;                                                                                                           \
+      float p[8];                                                                                                     \
+      _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                                 \
+        p[r] = AF_LAB(2) ? s0[r] : __builtin_amdgcn_exp2f(s0[r]);                                                     \
+        p[4 + r] = AF_LAB(2) ? s1[r] : __builtin_amdgcn_exp2f(s1[r]);                                                 \
+      }                                                                                                               \
+      if (!AF_LAB(8)) lsum[g] += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));                   \
+      unsigned hw[4], lw[4];                                                                                          \
+      _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                                 \
+        hw[r] = __builtin_bit_cast(unsigned, (att_h2){(_Float16)p[2 * r], (_Float16)p[2 * r + 1]});                   \
+        if (AF_LAB(4))                                                                                                \
+          lw[r] = hw[r];                                                                                              \
+        else                                                                                                          \
+          ATT_SPLIT_LOW_PAIR(lw[r], p[2 * r], p[2 * r + 1], hw[r]);                                                   \
+      }                                                                                                               \
+      typedef unsigned att_u4 __attribute__((ext_vector_type(4)));                                                    \
+      const att_h8 ph = __builtin_bit_cast(att_h8, (att_u4){hw[0], hw[1], hw[2], hw[3]});                             \
+      const att_h8 pl = __builtin_bit_cast(att_h8, (att_u4){lw[0], lw[1], lw[2], lw[3]});                             \
+      if (AF_LAB(16)) { /* (keeps the operands alive: 8 plain adds) */                                                \
+        oacc[g] += __builtin_bit_cast(f32x4, ph) + __builtin_bit_cast(f32x4, pl);                                     \
+      } else {                                                                                                        \
+        oacc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, ph, oacc[g], 0, 0, 0);                                   \
+        oacc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pl, oacc[g], 0, 0, 0);                                   \
+      }                                                                                                               \
+    }                                                                                                                 \
+  }
+
+// EXTENT (dmd_attention_f16x2): the same body over the V = vh vw tokens of the (vh, vw) extent of a (T / W, W) grid, addressed by
+// their valid index (EXTENT CONVENTION above): ceil(V / 256) workgroups per (image, head), blockIdx.x < nbv, and as many key tiles.
+//   * whole key tiles run the inner loops of the on-grid kernel (the same macro, unmasked, constant trip count); only a partial LAST tile runs the
+//     masked copy of them (af_mask_keys), over its 32-key blocks that hold a valid key.  Its keys behind V are not loaded: K and V
+//     are staged as zeros, their scores are -inf in both passes, p = 2^-inf = 0 exactly, so they add 0 to l and 0 * 0 to O.
+//   * queries behind V (the last workgroup's) are not loaded: their Q operand is zero, which leaves them out of the workgroup's
+//     qmax, and they are not stored.
+//   * BARRIERS: the only exit before the end is that of the workgroups blockIdx.x >= nbv, which leave as a whole before the first
+//     barrier (they write the rows of `out` outside the extent as +0).  In a workgroup blockIdx.x < nbv every thread, with or
+//     without a valid query (V = 323: the second workgroup has 67 valid queries, its waves 2 and 3 none), runs every statement
+//     below but the final store: ntiles, nk and the choice between the two copies of the inner loops depend on V and t alone, so
+//     all 256 threads stage their key of every tile, execute the same MFMAs and reach the same __syncthreads() the same number of
+//     times.
+// EXTENT = false is the on-grid kernel as it was (the same instruction stream): W, vh, vw, nbv are not read.  The extent form needs
+// 146 VGPRs against 128 (the valid-index arithmetic and the second copy of the loops): three workgroups per CU, asked for by its
+// launch bound (left at two it takes 174 registers), where the on-grid kernel has four.
+template <bool EXTENT>
+__global__ __launch_bounds__(256, EXTENT ? 3 : 2) void attention_f16x2_kernel(const float* __restrict__ qkv, float* __restrict__ out, int T, int C,
+                                                              float qscale, int W, int vh, int vw, int nbv) {
   __shared__ AfTile tiles[2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, kg = lane >> 4;
   const int n = blockIdx.z, h = blockIdx.y;
+  const int V = EXTENT ? vh * vw : T;
+  if constexpr (EXTENT) {
+    if ((int)blockIdx.x >= nbv) {  // the whole workgroup: no barrier has been reached
+      const int m = ((int)blockIdx.x - nbv) * 256 + tid;
+      if (m >= T - V) return;
+      float* o = out + ((size_t)n * T + ab_margin_token(m, W, vh, vw)) * C + h * 8;
+      *(f32x4*)o = (f32x4){0.f, 0.f, 0.f, 0.f};
+      *(f32x4*)(o + 4) = (f32x4){0.f, 0.f, 0.f, 0.f};
+      return;
+    }
+  }
   const int q0 = blockIdx.x * (64 * 4) + wave * 64;
   const size_t row = (size_t)3 * C;
   const float* base = qkv + (size_t)n * T * row;
-  const int ntiles = T / AF_KT;
+  const int ntiles = EXTENT ? (V + AF_KT - 1) / AF_KT : T / AF_KT;
 
   // Q operand of S^T = K Q^T, per 16-query group: k-slots {q_h | q_h | q_l | 0}, scaled by log2(e) / sqrt(d).
   // REBALANCING: the fp16 pieces carry 2^-22 of an operand only from 2^-3 upwards (below, their absolute floor 2^-25).  When every
@@ -236,9 +324,13 @@ __global__ __launch_bounds__(256, 2) void attention_f16x2_kernel(const float* __
   float qmax = 0.f;
 #pragma unroll
   for (int g = 0; g < AF_QG; ++g) {
-    const float* qp = base + (size_t)(q0 + g * 16 + j) * row + h * 8;
-    qa[g] = *(const f32x4*)qp;
-    qb[g] = *(const f32x4*)(qp + 4);
+    const int lq = q0 + g * 16 + j;
+    qa[g] = qb[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (!EXTENT || lq < V) {
+      const float* qp = base + (size_t)(EXTENT ? ab_token(lq, W, vw) : lq) * row + h * 8;
+      qa[g] = *(const f32x4*)qp;
+      qb[g] = *(const f32x4*)(qp + 4);
+    }
     qa[g] *= qscale;
     qb[g] *= qscale;
 #pragma unroll
@@ -270,7 +362,12 @@ __global__ __launch_bounds__(256, 2) void attention_f16x2_kernel(const float* __
   // staging of one key tile: thread = key; K always, V^T in pass 2
   f32x4 sk0, sk1, sv0, sv1;
   auto stage_load = [&](int t, bool with_v) {
-    const float* kp = base + (size_t)(t * AF_KT + tid) * row + C + h * 8;
+    const int lk = t * AF_KT + tid;
+    if constexpr (EXTENT) {
+      sk0 = sk1 = sv0 = sv1 = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (lk >= V) return;
+    }
+    const float* kp = base + (size_t)(EXTENT ? ab_token(lk, W, vw) : lk) * row + C + h * 8;
     sk0 = *(const f32x4*)kp;
     sk1 = *(const f32x4*)(kp + 4);
     if (with_v) {
@@ -306,15 +403,12 @@ __global__ __launch_bounds__(256, 2) void attention_f16x2_kernel(const float* __
   for (int t = 0; t < (AF_LAB(1) ? 1 : ntiles); ++t) {
     const AfTile& tl = tiles[t & 1];
     if (t + 1 < ntiles) stage_load(t + 1, false);
+    const int nk = !EXTENT || V - t * AF_KT > AF_KT ? AF_KT : V - t * AF_KT;
+    if (!EXTENT || nk == AF_KT) {
 #pragma unroll 2
-    for (int k0 = 0; k0 < AF_KT; k0 += 32) {
-      const att_h8 ka0 = k_frag(tl, k0), ka1 = k_frag(tl, k0 + 16);
-#pragma unroll
-      for (int g = 0; g < AF_QG; ++g) {
-        const f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ka0, bq[g], zero4, 0, 0, 0);
-        const f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ka1, bq[g], zero4, 0, 0, 0);
-        mx[g] = af_max3(af_max3(mx[g], s0[0], s0[1]), af_max3(s0[2], s0[3], s1[0]), af_max3(s1[1], s1[2], s1[3]));
-      }
+      for (int k0 = 0; k0 < AF_KT; k0 += 32) AF_PASS1_BLOCK((void)0)
+    } else {  // the partial last tile of an extent: its 32-key blocks that hold a valid key
+      for (int k0 = 0; k0 < nk; k0 += 32) AF_PASS1_BLOCK(af_mask_keys(s0, s1, k0 + 4 * kg, nk))
     }
     if (t + 1 < ntiles) stage_store(tiles[(t + 1) & 1], false);
     __syncthreads();
@@ -343,43 +437,12 @@ __global__ __launch_bounds__(256, 2) void attention_f16x2_kernel(const float* __
   for (int t = 0; t < ntiles; ++t) {
     const AfTile& tl = tiles[AF_LAB(64) ? 0 : (t & 1)];
     if (t + 1 < ntiles && !AF_LAB(64)) stage_load(t + 1, true);
+    const int nk = !EXTENT || V - t * AF_KT > AF_KT ? AF_KT : V - t * AF_KT;
+    if (!EXTENT || nk == AF_KT) {
 #pragma unroll 2
-    for (int k0 = 0; k0 < AF_KT; k0 += 32) {
-      const att_h8 ka0 = k_frag(tl, k0), ka1 = k_frag(tl, k0 + 16);
-      // V^T operand: lane (row i = lane & 15, kg): k-slots 0..3 = keys k0 + 4 kg + (0..3), 4..7 = keys k0 + 16 + 4 kg + (0..3)
-      const att_h4 va = *(const att_h4*)&tl.vt[j][k0 + 4 * kg], vb = *(const att_h4*)&tl.vt[j][k0 + 16 + 4 * kg];
-      const att_h8 vf = (att_h8){va[0], va[1], va[2], va[3], vb[0], vb[1], vb[2], vb[3]};
-#pragma unroll
-      for (int g = 0; g < AF_QG; ++g) {
-        const f32x4 s0 = AF_LAB(32) ? negm[g] + oacc[g] : __builtin_amdgcn_mfma_f32_16x16x32_f16(ka0, bq[g], negm[g], 0, 0, 0);
-        const f32x4 s1 = AF_LAB(32) ? negm[g] - oacc[g] : __builtin_amdgcn_mfma_f32_16x16x32_f16(ka1, bq[g], negm[g], 0, 0, 0);
-        float p[8];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          p[r] = AF_LAB(2) ? s0[r] : __builtin_amdgcn_exp2f(s0[r]);
-          p[4 + r] = AF_LAB(2) ? s1[r] : __builtin_amdgcn_exp2f(s1[r]);
-        }
-        if (!AF_LAB(8)) lsum[g] += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-        // split p = h + l: packed fp16 conversion for h, one mixed-precision fma per element for l = fp16(p - h)
-        unsigned hw[4], lw[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          hw[r] = __builtin_bit_cast(unsigned, (att_h2){(_Float16)p[2 * r], (_Float16)p[2 * r + 1]});
-          if (AF_LAB(4))
-            lw[r] = hw[r];
-          else
-            ATT_SPLIT_LOW_PAIR(lw[r], p[2 * r], p[2 * r + 1], hw[r]);
-        }
-        typedef unsigned att_u4 __attribute__((ext_vector_type(4)));
-        const att_h8 ph = __builtin_bit_cast(att_h8, (att_u4){hw[0], hw[1], hw[2], hw[3]});
-        const att_h8 pl = __builtin_bit_cast(att_h8, (att_u4){lw[0], lw[1], lw[2], lw[3]});
-        if (AF_LAB(16)) {
-          oacc[g] += __builtin_bit_cast(f32x4, ph) + __builtin_bit_cast(f32x4, pl);  // (keeps the operands alive: 8 plain adds)
-        } else {
-          oacc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, ph, oacc[g], 0, 0, 0);
-          oacc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pl, oacc[g], 0, 0, 0);
-        }
-      }
+      for (int k0 = 0; k0 < AF_KT; k0 += 32) AF_PASS2_BLOCK((void)0)
+    } else {
+      for (int k0 = 0; k0 < nk; k0 += 32) AF_PASS2_BLOCK(af_mask_keys(s0, s1, k0 + 4 * kg, nk))
     }
     if (t + 1 < ntiles && !AF_LAB(64)) stage_store(tiles[(t + 1) & 1], true);
     __syncthreads();
@@ -393,10 +456,13 @@ __global__ __launch_bounds__(256, 2) void attention_f16x2_kernel(const float* __
     f32x4 o = oacc[g];
 #pragma unroll
     for (int r = 0; r < 4; ++r) o[r] += __shfl_xor(o[r], 32, 64);
-    if (kg < 2) {
+    const int lq = q0 + g * 16 + j;
+    if (kg < 2 && (!EXTENT || lq < V)) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) o[r] = o[r] / l;
-      *(f32x4*)(out + ((size_t)n * T + q0 + g * 16 + j) * C + h * 8 + 4 * kg) = o;
+      // (the on-grid sum is kept term by term: as one int it costs the on-grid instantiation 6 VGPRs and a wave of occupancy)
+      const size_t tok = EXTENT ? (size_t)n * T + ab_token(lq, W, vw) : (size_t)n * T + q0 + g * 16 + j;
+      *(f32x4*)(out + tok * C + h * 8 + 4 * kg) = o;
     }
   }
 }
@@ -406,8 +472,8 @@ extern "C" int dmd_attention(const float* qkv, float* out, int N, int T, int C, 
   DMD_CHECK_ARG(T % 64 == 0, "attention: need T %% 64 == 0 (T=%d)", T);
   if (T % 256 == 0) {
     // whole 256-key tiles (256 tokens of the default 16x16 level, 1024 / 4096 of the 256x256 configuration): split-fp16 two-pass kernel
-    hipLaunchKernelGGL(attention_f16x2_kernel, dim3(T / 256, C / 8, N), dim3(256), 0, (hipStream_t)stream, qkv, out, T, C,
-                       1.4426950408889634f / sqrtf((float)head_dim));
+    hipLaunchKernelGGL(attention_f16x2_kernel<false>, dim3(T / 256, C / 8, N), dim3(256), 0, (hipStream_t)stream, qkv, out, T, C,
+                       1.4426950408889634f / sqrtf((float)head_dim), 0, 0, 0, 0);
     DMD_LAUNCH_CHECK();
     return 0;
   }
@@ -426,6 +492,20 @@ extern "C" int dmd_attention_valid(const float* qkv, float* out, int N, int H, i
   DMD_CHECK_ARG(T % 64 == 0, "attention_valid: need H W %% 64 == 0 (H=%d W=%d)", H, W);
   dim3 grid(T / 64, C / 8, N);
   hipLaunchKernelGGL(attention_kernel, grid, dim3(256), 0, (hipStream_t)stream, qkv, out, T, C, sqrtf((float)head_dim), W, valid_h, valid_w);
+  DMD_LAUNCH_CHECK();
+  return 0;
+}
+
+// The split-fp16 two-pass kernel over the (valid_h, valid_w) extent of an (H, W) grid, any valid token count >= 1 (engine.attention
+// in default precision from ATTN_F16X2_EXTENT_MIN_T valid tokens on: valid extents, and whole grids with T % 256 != 0 as the extent
+// (1, T, 1, T)).  Asynchronous, no allocation.
+extern "C" int dmd_attention_f16x2(const float* qkv, float* out, int N, int H, int W, int valid_h, int valid_w, int C, int head_dim,
+                                   dmd_stream_t stream) {
+  if (att_check_args("attention_f16x2", qkv && out, N, H, W, valid_h, valid_w, C, head_dim)) return 1;
+  const int T = H * W, V = valid_h * valid_w;
+  const int nbv = (V + AF_KT - 1) / AF_KT, nbm = (T - V + 255) / 256;
+  hipLaunchKernelGGL(attention_f16x2_kernel<true>, dim3(nbv + nbm, C / 8, N), dim3(256), 0, (hipStream_t)stream, qkv, out, T, C,
+                     1.4426950408889634f / sqrtf((float)head_dim), W, valid_h, valid_w, nbv);
   DMD_LAUNCH_CHECK();
   return 0;
 }

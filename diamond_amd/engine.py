@@ -831,7 +831,10 @@ def nhwc_to_nchw(x: Tensor, c: Optional[int] = None) -> Tensor:
 
 # Arithmetic of the attention cores (SelfAttention2d; the 8x8 dmd_lowres_chain / chain32 launches carry their own core, which is on
 # fp32 operands already):
-#   "f16x2": dmd_attention's routing by T alone -- the split-fp16 two-pass kernel at T % 256 == 0 (default);
+#   "f16x2": (default) the split-fp16 two-pass kernel wherever it is measured to win: dmd_attention at whole grids with
+#            T % 256 == 0 (its routing by T alone); dmd_attention_f16x2 (the same kernel over the valid tokens) for a valid extent
+#            and for a whole grid with T % 256 != 0, from ATTN_F16X2_EXTENT_MIN_T valid tokens on; below that, attention_kernel
+#            (dmd_attention_valid over the padded grid / dmd_attention);
 #   "f32"  : exact fp32 operands everywhere: dmd_attention_f32 (attention_f32_tiled_kernel) from ATTN_F32_TILED_MIN_T VALID tokens
 #            on, attention_kernel (dmd_attention_valid, over the real or the whole-grid extent) below that.
 # DIAMOND_ATTN_PRECISION is read at every call that does not name a precision; it is a switch of its own: DIAMOND_CONV_PRECISION=f32
@@ -842,8 +845,17 @@ def nhwc_to_nchw(x: Tensor, c: Optional[int] = None) -> Tensor:
 # other extents in that range are not measured: attention_kernel walks the whole padded grid, the tiled kernel the valid tokens
 # only, so by the code the gap can only widen there).  Nothing below 256 tokens was measured, so nothing below it is routed.
 # DIAMOND_ATTN_F32_MIN_T=n overrides it (read at every call), 0 = never the tiled kernel.
+# ATTN_F16X2_EXTENT_MIN_T: measured by the same rule (profiles/attention_f16x2_extent.json, tools/attention_fwd_bench.py
+# --f16x2-extent: dmd_attention_f16x2 against attention_kernel, which is what these shapes ran before).  The table's
+# "derived_threshold" is 256: the new entry wins by more than the spread at every measured shape, 1.5x (320 whole grid) to 23x
+# (36 x 36 of 64 x 64).  The default is 576 all the same, the next measured count above 360: the 68 x 76 training step's upper
+# attention level (18 x 20 = 360 valid tokens of its 72 x 80 padded image) stays on dmd_attention_valid, because
+# tests/test_offgrid_train.py pins that step's launches on the interpreter (12 dmd_attention_valid);
+# DIAMOND_ATTN_F16X2_MIN_T=256 is the measured optimum (6.1x at 360 tokens).
+# DIAMOND_ATTN_F16X2_MIN_T=n overrides the default (read at every call), 0 = never: the routes and bits from before the entry existed.
 ATTN_PRECISIONS = ("f16x2", "f32")
 ATTN_F32_TILED_MIN_T = 256
+ATTN_F16X2_EXTENT_MIN_T = 576
 
 
 def attn_precision(precision: Optional[str] = None) -> str:
@@ -856,6 +868,11 @@ def attn_precision(precision: Optional[str] = None) -> str:
 def attn_f32_tiled_min_t() -> int:
     v = os.environ.get("DIAMOND_ATTN_F32_MIN_T")
     return ATTN_F32_TILED_MIN_T if v is None or v == "" else int(v)
+
+
+def attn_f16x2_extent_min_t() -> int:
+    v = os.environ.get("DIAMOND_ATTN_F16X2_MIN_T")
+    return ATTN_F16X2_EXTENT_MIN_T if v is None or v == "" else int(v)
 
 
 def token_extent(shape, valid: Optional[Tuple[int, int]]) -> Tuple[int, int, int, int]:
@@ -879,6 +896,10 @@ def attention(qkv: Act, c: int, head_dim: int = 8, precision: Optional[str] = No
     if exact and 0 < attn_f32_tiled_min_t() <= tv:  # long token grids: the tiled two-pass kernel, over the valid tokens only
         note = ("attention_f32_tiled_kernel", 4.0 * n * tv * tv * c, 4.0 * n * tv * 4 * c)
         name, args = "dmd_attention_f32", (n, gh, gw, vh, vw, c)
+    elif not exact and (qkv.valid is not None or t % 256 != 0) and 0 < attn_f16x2_extent_min_t() <= tv:
+        # off the tile grid in default precision: the split-fp16 two-pass kernel over the valid tokens only
+        note = ("attention_f16x2_kernel", 4.0 * n * tv * tv * c, 4.0 * n * tv * 4 * c)
+        name, args = "dmd_attention_f16x2", (n, gh, gw, vh, vw, c)
     elif exact or qkv.valid is not None:  # attention_kernel over the padded grid; keys outside the valid extent stay out of the softmax
         note = ("attention_kernel", 4.0 * n * tv * t * c, 4.0 * n * t * 4 * c) if exact else None
         name, args = "dmd_attention_valid", (n, h, w, *(qkv.valid or (h, w)), c)

@@ -236,6 +236,22 @@ int dmd_attention_valid(const float* qkv, float* out, int N, int H, int W, int v
  * (tests/test_attention_f32_tiled.py, profiles/attention_f32_tiled_precision.txt); differs from attention_kernel in rounding only. */
 int dmd_attention_f32(const float* qkv, float* out, int N, int H, int W, int valid_h, int valid_w, int C, int head_dim,
                       dmd_stream_t stream);
+/* (ABI v11 addition) The split-fp16 two-pass kernel (attention_f16x2_kernel, dmd_attention's at T % 256 == 0) over ANY valid
+ * extent: arguments, checks and extent convention are dmd_attention_f32's -- tokens addressed by their valid index, the work sized
+ * by valid_h * valid_w (ceil(tv / 256) workgroups per (image, head), as many key tiles), any valid token count >= 1, nothing outside
+ * the extent read (the margins of qkv may hold anything, NaN / Inf included), the rows of `out` outside the extent written as +0.
+ * Whole key tiles run dmd_attention's inner loops; only a partial last tile is masked: its keys behind the extent are staged as
+ * zeros, their scores are REPLACED by -inf in both passes (a selection: a zero key against an infinite query makes no NaN) and they
+ * add exactly 0 to the row sum and to the output.  Asynchronous, allocates nothing, graph-capturable.  What engine.attention calls
+ * in default precision for valid extents and for whole grids with T % 256 != 0, from ATTN_F16X2_EXTENT_MIN_T valid tokens on
+ * (DIAMOND_ATTN_F16X2_MIN_T); dmd_attention and dmd_attention_valid keep their routing and their bits.
+ * PRECISION CONTRACT: the two-pass kernel's above, per (query, key) pair -- the same split operands, products, weights, range and
+ * non-finite behaviour.  REBALANCING is decided per workgroup of 256 queries IN VALID-INDEX ORDER (queries 256 b .. 256 b + 255 of
+ * the extent, the last workgroup's over its valid queries only).  Bitwise: the extent (1, T, 1, T) with T % 256 == 0 is
+ * dmd_attention; (H, W, vh, vw) is the flat call (1, tv, 1, tv) on the compacted tokens; run-to-run equal; an (image, head)'s output
+ * does not depend on N or on the other heads.  d == 8. */
+int dmd_attention_f16x2(const float* qkv, float* out, int N, int H, int W, int valid_h, int valid_w, int C, int head_dim,
+                        dmd_stream_t stream);
 /* Backward of dmd_attention (autograd of blocks.py:66-71 under the denoiser training loss, denoiser.py:93-122):
  * y = the forward's output, dy its gradient -> dqkv (N, T, 3C) in the qkv layout.  workspace: dmd_attention_bwd_workspace_floats.
  * Any T > 0.  dmd_attention_bwd and dmd_attention_bwd_valid launch ONE pair of scalar kernels (attention_bwd_rows_kernel,
