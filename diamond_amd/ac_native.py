@@ -16,6 +16,7 @@ The LSTM cell and the two heads downstream run on dmd_linear / dmd_lstm_pointwis
 from __future__ import annotations
 
 import os
+import weakref
 from typing import List, Optional, Tuple
 
 import torch
@@ -91,6 +92,15 @@ class _Plan:
             self.params += [gn.weight, gn.bias, conv.weight, conv.bias]
             if not isinstance(blk.skip_projection, nn.Identity):
                 self.params += [blk.skip_projection.weight, blk.skip_projection.bias]
+        # the flat gradient buffer of a backward: the parameters' gradients back to back in this order (sizes[i] floats each);
+        # block j's parameters start at index block_first[j]
+        self.sizes: List[int] = [p.numel() for p in self.params]
+        self.numel = sum(self.sizes)
+        self.block_first: List[int] = []
+        i = 2
+        for blk, _ in self.blocks:
+            self.block_first.append(i)
+            i += 4 if isinstance(blk.skip_projection, nn.Identity) else 6
 
 
 class _EncoderFn(torch.autograd.Function):
@@ -125,6 +135,7 @@ class _EncoderFn(torch.autograd.Function):
             saved.append((x, arg))
             x = nxt
         ctx.plan, ctx.cache, ctx.x16, ctx.saved = plan, cache, Act(x16, valid=valid), saved
+        ctx.bundled = len(params) != len(plan.params)  # (the parameters arrive as one _ParamBundleFn output)
         ctx.cimg = cimg
         ctx.out_valid, ctx.out_buf = x.valid, tuple(x.shape[1:3])
         # flatten in the reference's (c, h, w) order (actor_critic.py:71)
@@ -133,6 +144,10 @@ class _EncoderFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dfeat: Tensor):
+        """Parameter gradients: every weight / bias gradient and every GroupNorm parameter gradient of this backward is a slice of
+        ONE flat fp32 buffer (in the order of plan.params), written by ONE dmd_wgrad_reduce_jobs launch at the end, which also
+        applies the 2^-k of the scaled backward.  With the parameter bundle (_ParamBundleFn) the flat buffer is the one gradient
+        this node returns; without it (DIAMOND_AC_GRAD_BUNDLE=0) the per-parameter views of it are returned, same bits."""
         plan, cache = ctx.plan, ctx.cache
         split = AC_PRECISION == "f16x2"  # weight gradients in the split-fp16 form too (exact fp32 with DIAMOND_AC_PRECISION=f32)
         blk_last, _ = plan.blocks[-1]
@@ -144,48 +159,93 @@ class _EncoderFn(torch.autograd.Function):
         dfeat, inv_scale = G.pow2_scaled(dfeat)
         dfeat, _ = E.pad_to_extent(dfeat.reshape(n, cl, hl, wl), hb, wb)  # zero gradient outside the valid extent of the last buffer
         dcur = E.nchw_to_nhwc(dfeat.contiguous())
-        grads_rev: List[Optional[Tensor]] = []
-        # (the reductions of this backward's weight gradients as ONE launch at its end instead of two per gradient: same sums)
-        batch = G.wgrad_batch()
+        # (the reductions of this backward's weight gradients as ONE launch at its end instead of two per gradient: same sums;
+        #  the launch multiplies by 2^-k as it writes: bitwise the multiplication pass it replaces)
+        batch = G.wgrad_batch(inv_scale.reshape(1))
+        flat = torch.empty(plan.numel, device=dfeat.device, dtype=torch.float32)
+        # out[i] = the gradient of plan.params[i]: ONE split call (a view per parameter costs host time on a host-paced stretch);
+        # the kernels take the 1-D pieces, only a convolution weight's is viewed in its OIHW shape (the reduction's row length)
+        out = list(flat.split_with_sizes(plan.sizes))
 
-        def wgrad(src, prologue, spec_, dy_, taps, cin):
+        def wgrad(src, prologue, spec_, dy_, taps, cin, i):
+            """dW, db into out[i], out[i + 1]"""
+            out[i] = out[i].view(plan.params[i].shape)
             if batch is None:
-                return G.wgrad(src, prologue, spec_, dy_, taps, cin, split=split)
-            kk = 3 if taps == 9 else 1
-            return G.wgrad(src, prologue, spec_, dy_, taps, cin, split=split, batch=batch,
-                           dw_out=torch.empty(dy_.shape[-1], cin, kk, kk, device=dy_.device, dtype=torch.float32),
-                           db_out=torch.empty(dy_.shape[-1], device=dy_.device, dtype=torch.float32))
+                dw_, db_ = G.wgrad(src, prologue, spec_, dy_, taps, cin, split=split)
+                torch.mul(dw_, inv_scale, out=out[i])
+                torch.mul(db_, inv_scale, out=out[i + 1])
+                return
+            G.wgrad(src, prologue, spec_, dy_, taps, cin, split=split, batch=batch, dw_out=out[i], db_out=out[i + 1])
+            if not G._wgrad_instance(dy_.shape[-1], src.C, taps):
+                # (a width the kernel has no instance for is reduced tile by tile at once, not by the batch: scaled here)
+                out[i].mul_(inv_scale)
+                out[i + 1].mul_(inv_scale)
 
-        for (blk, pool), (x, arg) in zip(reversed(plan.blocks), reversed(ctx.saved)):
+        for (blk, pool), (x, arg), i0 in zip(reversed(plan.blocks), reversed(ctx.saved), reversed(plan.block_first)):
+            # out[i0 ...] = [gn.weight, gn.bias, conv.weight, conv.bias, (skip.weight, skip.bias)]
             gn, conv = blk.f[0].norm, blk.f[2]
             spec = NormSpec(mul=cache.f32(gn.weight), add=cache.f32(gn.bias))
             dy = G.maxpool_bwd(dcur, arg) if pool else dcur
-            dw, db = wgrad(x, nv.PROLOGUE_NORM_SILU, spec, dy, 9, conv.in_channels)
+            wgrad(x, nv.PROLOGUE_NORM_SILU, spec, dy, 9, conv.in_channels, i0 + 2)
             vy = x.valid  # (a stride-1 block: its output exists where its input does; dy is zero elsewhere, and is treated so)
             # (split-fp16 pieces of the transposed weight: asked for the 3x3 stride-1 convolutions only, none for the 1x1 projection)
             wt, wt16 = G.dgrad_weights(cache, conv, 0, conv.in_channels, f16x2=split and conv.kernel_size == (3, 3) and conv.stride == (1, 1))
             da = E.conv2d([(Act(dy, valid=vy), nv.PROLOGUE_NONE, None)], wt, None, conv.in_channels, want_stats=False, w_f16=wt16).t
             sp = blk.skip_projection
-            g_skip: List[Optional[Tensor]] = []
             if isinstance(sp, nn.Identity):
                 dskip = dy
             else:
-                dws, dbs = wgrad(x, nv.PROLOGUE_NONE, None, dy, 1, sp.in_channels)
+                wgrad(x, nv.PROLOGUE_NONE, None, dy, 1, sp.in_channels, i0 + 4)
                 dskip = E.conv2d([(Act(dy, valid=vy), nv.PROLOGUE_NONE, None)], G.dgrad_weights(cache, sp, 0, sp.in_channels)[0], None,
                                  sp.in_channels, taps=1, want_stats=False).t
-                g_skip = [dws, dbs]
             dx, dma = G.gn_bwd(x, spec, da, dskip)
-            # reversed order of [gn.weight, gn.bias, conv.weight, conv.bias, (skip.weight, skip.bias)]
-            dms = dma.sum(1)  # (2, C): both batch sums with one reduction (same per-column order as two .sum(0))
-            grads_rev += list(reversed([dms[0], dms[1], dw, db] + g_skip))
+            # dgamma, dbeta = the sums of dma (2, N, C) over the batch: a job of the same launch (ascending n, fp64 accumulation);
+            # with DIAMOND_WGRAD_DEFER=0 a launch of its own, the same kernel: the same bits
+            gn_batch = batch if batch is not None else G.WgradBatch(inv_scale.reshape(1))
+            gn_batch.add_colsum(dma, out[i0], out[i0 + 1])
+            if batch is None:
+                gn_batch.flush()
             dcur = dx
-        ci = plan.conv_in
-        dw_in, db_in = wgrad(ctx.x16, nv.PROLOGUE_NONE, None, dcur, 9, ctx.cimg)
+        wgrad(ctx.x16, nv.PROLOGUE_NONE, None, dcur, 9, ctx.cimg, 0)
         if batch is not None:
             batch.flush()
-        # (one multi-tensor launch instead of one broadcast multiplication per gradient: 18 per step, 270 per window)
-        grads = torch._foreach_mul([dw_in, db_in] + list(reversed(grads_rev)), inv_scale)
-        return (None, None, None, *grads)
+        if ctx.bundled:
+            return (None, None, None, flat)
+        return (None, None, None, *[g.view(p.shape) for g, p in zip(out, plan.params)])
+
+
+class _ParamBundleFn(torch.autograd.Function):
+    """The autograd edge between the encoder's parameters and the _EncoderFn nodes of ONE recorded graph: its output stands for
+    all of plan.params (a flat fp32 buffer of their total size whose VALUES nobody reads: _EncoderFn.forward takes the weights
+    from the pack cache), its backward splits the flat gradient into per-parameter views.  Every _EncoderFn.backward of the graph
+    returns one flat gradient; autograd sums the 15 steps' with one add per step instead of one per parameter and step, and
+    AccumulateGrad -- and any post-accumulate hook (dist.GradAllReducer) -- runs once per parameter and backward.
+
+    Summation order across the steps of a window: autograd adds the gradients that reach a node in that node's input buffer as
+    their producers run, last step first, and runs the node once: S = ((g14 + g13) + ...) + g0 elementwise, then AccumulateGrad
+    forms .grad = G + S for a .grad G that exists already (S itself where .grad is None).  That is the order with and without
+    the bundle -- without it the sum S is formed per parameter in that parameter's AccumulateGrad input buffer, with it once on
+    the flat buffer in this node's -- so every .grad is bitwise the same either way, also on top of a non-zero G carried over
+    from gradient accumulation."""
+
+    @staticmethod
+    def forward(ctx, owner_ref, plan: _Plan, *params: Tensor) -> Tensor:
+        ctx.owner_ref, ctx.plan = owner_ref, plan
+        return torch.empty(plan.numel, device=params[0].device, dtype=torch.float32)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        owner = ctx.owner_ref()
+        if owner is not None:
+            owner._bundle = None  # the graph is consumed: the next recorded graph gets its own node
+        plan = ctx.plan
+        return (None, None, *[piece.view(p.shape) for piece, p in zip(g.split_with_sizes(plan.sizes), plan.params)])
+
+
+def grad_bundle_enabled() -> bool:
+    """DIAMOND_AC_GRAD_BUNDLE=0: one gradient per encoder parameter and _EncoderFn node, accumulated by autograd parameter by
+    parameter (the A/B arm; same bits from a zero or absent .grad)."""
+    return os.environ.get("DIAMOND_AC_GRAD_BUNDLE", "1") != "0"
 
 
 class NativeEncoder:
@@ -194,7 +254,15 @@ class NativeEncoder:
     def __init__(self, encoder_seq: nn.Sequential) -> None:
         self.plan = _Plan(encoder_seq)
         self.cache = E.PackCache()
+        self._bundle: Optional[Tensor] = None  # the _ParamBundleFn output of the graph being recorded (reset by its backward)
+        self._bundle_key = None
 
     def __call__(self, obs: Tensor) -> Tensor:
         nv.require_gpu(obs)
-        return _EncoderFn.apply(self.plan, self.cache, obs.contiguous(), *self.plan.params)
+        params = self.plan.params
+        if grad_bundle_enabled() and torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            key = tuple(p.requires_grad for p in params) + (params[0].device,)
+            if self._bundle is None or self._bundle_key != key:
+                self._bundle, self._bundle_key = _ParamBundleFn.apply(weakref.ref(self), self.plan, *params), key
+            return _EncoderFn.apply(self.plan, self.cache, obs.contiguous(), self._bundle)
+        return _EncoderFn.apply(self.plan, self.cache, obs.contiguous(), *params)

@@ -1451,9 +1451,27 @@ struct wgrad_job_batch {
 
 __global__ __launch_bounds__(256) void wgrad_reduce_jobs_kernel(const wgrad_job_batch b) {
   const dmd_wgrad_reduce_job& j = b.job[blockIdx.y];
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  // job.scale (device, or NULL): the gradient leaves as (float)sum * *scale -- the 2^-k of a backward that ran on a gradient
+  // scaled by 2^k: a power of two, so bitwise the unscaled reduction followed by a multiplication pass
+  if (j.kind == DMD_REDUCE_COLSUM) {
+    // GroupNorm parameter gradients: the per-(sample, channel) gradients [dmul; dadd] (2, N, C) of dmd_gn_silu_bwd summed over
+    // the N samples, one thread per (which, channel), ascending n, in fp64 like the reductions above -> dw[c] = dgamma,
+    // dbias[c] = dbeta.  (N = num_wg, C = cin_real.)  Consecutive threads read consecutive channels: coalesced.
+    const int C = j.cin_real, N = j.num_wg;
+    if (idx >= 2 * C) return;
+    const int which = idx >= C, c = idx - which * C;
+    const float* __restrict__ src = j.partials + (size_t)which * N * C + c;
+    double s = 0.0;
+#pragma unroll 4
+    for (int n = 0; n < N; ++n) s += (double)src[(size_t)n * C];
+    float v = (float)s;
+    if (j.scale) v *= *j.scale;
+    (which ? j.dbias : j.dw)[c] = v;
+    return;
+  }
   const int per = j.NB * j.NCO * 256;
   const int per_total = per + j.NCO * 16;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= per_total) return;
   const float* __restrict__ ws = j.partials;
   double s = 0.0;
@@ -1468,6 +1486,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce_jobs_kernel(const wgrad_job_
       s += (double)f;
     }
   }
+  float v = (float)s;
+  if (j.scale) v *= *j.scale;
   if (idx < per) {
     const int r = idx & 3, lane = (idx >> 2) & 63;
     const int blk = idx >> 8;
@@ -1475,9 +1495,9 @@ __global__ __launch_bounds__(256) void wgrad_reduce_jobs_kernel(const wgrad_job_
     const int tap = bb / j.NCI, cib = bb - tap * j.NCI;
     const int co = cob * 16 + 4 * (lane >> 4) + r;
     const int ci = cib * 16 + (lane & 15);
-    if (ci < j.cin_real) j.dw[((size_t)co * j.ld_cin + j.c0 + ci) * j.taps + tap] = (float)s;
+    if (ci < j.cin_real) j.dw[((size_t)co * j.ld_cin + j.c0 + ci) * j.taps + tap] = v;
   } else if (j.dbias) {
-    j.dbias[idx - per] = (float)s;
+    j.dbias[idx - per] = v;
   }
 }
 
@@ -1588,6 +1608,9 @@ extern "C" int dmd_wgrad_job(const dmd_wgrad_params* p, dmd_wgrad_reduce_job* jo
   job->cin_real = p->cin_real;
   job->ld_cin = p->cin_real;  // (the caller widens these two for a gradient that is a slice of a larger OIHW tensor)
   job->c0 = 0;
+  job->scale = nullptr;
+  job->kind = DMD_REDUCE_WGRAD;
+  job->reserved = 0;
   return 0;
 }
 
@@ -1601,6 +1624,13 @@ extern "C" int dmd_wgrad_reduce_jobs(const dmd_wgrad_reduce_job* jobs, int njobs
     int max_total = 0;
     for (int i = 0; i < n; ++i) {
       const dmd_wgrad_reduce_job& j = jobs[j0 + i];
+      DMD_CHECK_ARG(j.kind == DMD_REDUCE_WGRAD || j.kind == DMD_REDUCE_COLSUM, "wgrad reduce jobs: job %d: kind %d", j0 + i, j.kind);
+      if (j.kind == DMD_REDUCE_COLSUM) {
+        DMD_CHECK_ARG(j.partials && j.dw && j.dbias && j.num_wg > 0 && j.cin_real > 0, "wgrad reduce jobs: column-sum job %d malformed", j0 + i);
+        b.job[i] = j;
+        if (2 * j.cin_real > max_total) max_total = 2 * j.cin_real;
+        continue;
+      }
       DMD_CHECK_ARG(j.partials && j.dw && j.num_wg > 0 && j.num_wg <= 1024 && j.NCO > 0 && j.NCI > 0 && (j.taps == 9 || j.taps == 1) &&
                         j.NB == j.taps * j.NCI,
                     "wgrad reduce jobs: job %d malformed", j0 + i);

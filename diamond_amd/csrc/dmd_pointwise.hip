@@ -675,6 +675,41 @@ __global__ void merge_slots_bwd_kernel(const float* __restrict__ d_out, const in
   }
 }
 
+// TD(lambda) targets of the actor-critic loss (reference actor_critic.py:116-143; diamond_amd/actor_critic.py
+// compute_lambda_returns): one thread per env row runs the backward recursion over the T steps of the window, which the host code
+// spells as a Python loop of four (B,) launches per step.  The fp32 operations are those of the torch expressions, in their order
+// (the file is compiled with -ffp-contract=off: no product is fused into an add):
+//   ret[t]  = sign(rew) + ((float(1 - end) * g) * ((float(1 - trunc) * (1 - lambda)) + float(trunc))) * v[t]
+//   ret[t] += ((alive * g) * lambda) * last,   last = v[T - 1], then ret[t + 1];   alive = !min(end + trunc, 1)
+// g, 1 - lambda (formed in double by the host, like Python does) and lambda arrive rounded to fp32, as torch rounds a Python scalar.
+__global__ void lambda_returns_kernel(const float* __restrict__ rew, const int64_t* __restrict__ end, const int64_t* __restrict__ trunc,
+                                      const float* __restrict__ vb, float* __restrict__ ret, int B, int T, float g,
+                                      float one_minus_lambda, float lambda) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const size_t row = (size_t)b * T;
+  float last = vb[row + T - 1];
+  for (int t = T - 1; t >= 0; --t) {
+    const float r = rew[row + t];
+    const int64_t e = end[row + t], tr = trunc[row + t];
+    const float sgn = (float)((0.f < r) - (r < 0.f));
+    const float x1 = (float)(1 - e) * g;
+    const float x2 = (float)(1 - tr) * one_minus_lambda;
+    const float x3 = x2 + (float)tr;
+    const float x4 = x1 * x3;
+    const float x5 = x4 * vb[row + t];
+    float v = sgn + x5;
+    const int64_t d = e + tr;
+    const float alive = (d < 1 ? d : 1) == 0 ? 1.f : 0.f;
+    const float a1 = alive * g;
+    const float a2 = a1 * lambda;
+    const float a3 = a2 * last;
+    v = v + a3;
+    ret[row + t] = v;
+    last = v;
+  }
+}
+
 extern "C" int dmd_merge_slots(const float* base, const float* slots, const int32_t* row_slot, float* out, int B, int D, dmd_stream_t stream) {
   DMD_CHECK_ARG(base && slots && row_slot && out && B >= 1 && D >= 1, "merge_slots: args");
   hipLaunchKernelGGL(merge_slots_kernel, dim3(nblk((size_t)B * D, 256)), dim3(256), 0, (hipStream_t)stream, base, slots, row_slot, out, B, D);
@@ -754,6 +789,15 @@ extern "C" int dmd_lstm_pointwise_bwd(const float* gates, const float* c_prev, c
   DMD_CHECK_ARG(gates && c_prev && c_new && dgates && dc_prev, "lstm_pointwise_bwd: null");
   hipLaunchKernelGGL(lstm_pointwise_bwd_kernel, dim3(nblk((size_t)N * Hd, 256)), dim3(256), 0, (hipStream_t)stream, gates,
                      c_prev, c_new, dh, dc, dgates, dc_prev, N, Hd);
+  DMD_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int dmd_lambda_returns(const float* rew, const int64_t* end, const int64_t* trunc, const float* val_bootstrap, float* ret, int B,
+                                  int T, float gamma, float one_minus_lambda, float lambda, dmd_stream_t stream) {
+  DMD_CHECK_ARG(rew && end && trunc && val_bootstrap && ret && B >= 1 && T >= 1, "lambda_returns: args");
+  hipLaunchKernelGGL(lambda_returns_kernel, dim3(nblk((size_t)B, 64)), dim3(64), 0, (hipStream_t)stream, rew, end, trunc, val_bootstrap,
+                     ret, B, T, gamma, one_minus_lambda, lambda);
   DMD_LAUNCH_CHECK();
   return 0;
 }

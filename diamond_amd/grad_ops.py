@@ -70,15 +70,35 @@ def maxpool_bwd(dp: Tensor, arg: Tensor) -> Tensor:
 class WgradBatch:
     """Weight gradients whose reductions wait for ONE launch per 32 of them (`dmd_wgrad_reduce_jobs`, ABI v10): the backward of a
     denoiser training step holds ~60 weight gradients nobody reads before it is over, and their reductions were ~140 launches
-    of a few microseconds of work.  The sums are formed in the undeferred order: bit-identical gradients."""
+    of a few microseconds of work.  The sums are formed in the undeferred order: bit-identical gradients.
 
-    def __init__(self) -> None:
+    scale (a one-element fp32 DEVICE tensor, or None): every gradient of the batch leaves the launch multiplied by it -- the 2^-k
+    of a backward that ran under pow2_scaled: bitwise the reduction followed by a multiplication pass, without the pass.
+    add_colsum: the GroupNorm parameter gradients of a block ride in the same launch (DMD_REDUCE_COLSUM)."""
+
+    def __init__(self, scale: Optional[Tensor] = None) -> None:
         self.jobs: List[nv.WgradReduceJob] = []
         self._keep: List[Tensor] = []  # the workspaces holding the partials (and the outputs) until flush()
+        self.scale = scale
+        if scale is not None:
+            assert scale.numel() == 1 and scale.dtype == torch.float32
+            self._keep.append(scale)
 
     def add(self, job: "nv.WgradReduceJob", *keep: Tensor) -> None:
+        if self.scale is not None:
+            job.scale = nv.ptr(self.scale)
         self.jobs.append(job)
         self._keep.extend(keep)
+
+    def add_colsum(self, dma: Tensor, dgamma: Tensor, dbeta: Tensor) -> None:
+        """dgamma[c] = sum_n dma[0, n, c], dbeta[c] = sum_n dma[1, n, c] (dma: gn_bwd's (2, N, C)): ascending n, fp64 accumulation,
+        one rounding to fp32 (then the batch's scale).  Deterministic; not torch's reduction order."""
+        two, n, c = dma.shape
+        assert two == 2 and dma.is_contiguous() and dma.dtype == torch.float32 and dgamma.numel() == dbeta.numel() == c \
+            and dgamma.is_contiguous() and dbeta.is_contiguous()
+        job = nv.WgradReduceJob()
+        job.kind, job.partials, job.dw, job.dbias, job.num_wg, job.cin_real = nv.REDUCE_COLSUM, nv.ptr(dma), nv.ptr(dgamma), nv.ptr(dbeta), n, c
+        self.add(job, dma, dgamma, dbeta)
 
     def flush(self) -> None:
         if self.jobs:
@@ -87,10 +107,10 @@ class WgradBatch:
         self.jobs, self._keep = [], []
 
 
-def wgrad_batch() -> Optional[WgradBatch]:
+def wgrad_batch(scale: Optional[Tensor] = None) -> Optional[WgradBatch]:
     """The batch a backward pass defers its weight-gradient reductions to; DIAMOND_WGRAD_DEFER=0: None, every gradient is
-    reduced by its own call (same sums)."""
-    return WgradBatch() if os.environ.get("DIAMOND_WGRAD_DEFER", "1") == "1" else None
+    reduced by its own call (same sums).  scale: see WgradBatch."""
+    return WgradBatch(scale) if os.environ.get("DIAMOND_WGRAD_DEFER", "1") == "1" else None
 
 
 # (output channels / 16, input channels / 16) the weight-gradient kernel is instantiated for (csrc/dmd_backward.hip:

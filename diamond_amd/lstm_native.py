@@ -4,8 +4,8 @@
 
 One `torch.autograd.Function` per policy step: gate GEMMs and head GEMM on `dmd_linear` (v_mfma_f32_16x16x4_f32, exact
 fp32 fma chains), gate nonlinearity in `dmd_lstm_pointwise`; the backward is `dmd_lstm_pointwise_bwd` plus the
-transposed GEMMs, again on `dmd_linear` -- its operands are K-contiguous ("NT"), so the data/weight gradients use
-transposed copies of the (small) activation matrices and version-cached transposed weights.  BPTT over the 15-step
+transposed GEMMs, again on `dmd_linear` -- which takes an operand in either storage order, so the weight gradients read the
+activation matrices where they lie (no transposed copies); the data gradients use version-cached transposed weights.  BPTT over the 15-step
 window is torch's ordinary chaining of these Functions through (hx, cx).
 """
 from __future__ import annotations
@@ -20,17 +20,10 @@ from . import engine as E
 from . import native as nv
 
 
-def _pad_k(t: Tensor) -> Tensor:
-    """(M, K) -> contiguous (M, K rounded up to 16) (dmd_linear contracts over multiples of 16)."""
-    k = t.shape[1]
-    kp = (k + 15) // 16 * 16
-    t = t.contiguous()
-    return t if kp == k else F.pad(t, (0, kp - k))
-
-
 def _mm_nt(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
-    """a (M, K) @ w (N, K)^T on dmd_linear, K zero-padded to a multiple of 16."""
-    a, w = _pad_k(a), _pad_k(w)
+    """a (M, K) @ w (N, K)^T on dmd_linear.  The operands are read where they are: a transposed view (`g.t()` of a row-major
+    matrix) goes in as that matrix with the transposed flag, and a K that is no multiple of 16 is masked in the kernel -- bitwise
+    the result on `.t().contiguous()` copies zero-padded along K, which this function used to make."""
     return E.linear(a, w, bias, out=out, accumulate=accumulate)
 
 
@@ -63,8 +56,9 @@ class LstmHeadsFn(torch.autograd.Function):
         if dheads is not None:
             dheads = dheads.detach().float().contiguous()
             # dh += dheads @ W_heads ; dW_heads = dheads^T @ h ; db_heads = sum dheads
-            wt = w_heads.detach().t().contiguous()  # (hd, A + 1)
-            dh_total = _mm_nt(dheads, wt, out=dh_total.clone() if dh_total is not None else None, accumulate=dh_total is not None)
+            # (the clone stays: dh is autograd's buffer, which another consumer may hold, and the GEMM accumulates in place)
+            dh_total = _mm_nt(dheads, w_heads.detach().t(), out=dh_total.clone() if dh_total is not None else None,
+                              accumulate=dh_total is not None)
             dw_heads = _mm_nt(dheads.t(), h.t())
             db_heads = dheads.sum(0)
         dgates = torch.empty_like(gates)
@@ -77,7 +71,7 @@ class LstmHeadsFn(torch.autograd.Function):
             dx = _mm_nt(dgates, ctx.w_ih_t)
         if need[2]:
             dhx = _mm_nt(dgates, ctx.w_hh_t)
-        dgt = dgates.t().contiguous()
+        dgt = dgates.t()
         dw_ih = _mm_nt(dgt, x.t())
         dw_hh = _mm_nt(dgt, hx.t())
         db = dgates.sum(0)
@@ -184,10 +178,10 @@ class LstmBurnInFn(torch.autograd.Function):
             if i > 0:
                 dhc = _mm_nt(dg, ctx.w_hh_t)
         dx = _mm_nt(dgates, ctx.w_ih_t) if ctx.needs_input_grad[1] else None
-        dgt = dgates.t().contiguous()
+        dgt = dgates.t()
         dw_ih = _mm_nt(dgt, x.t())
         # (frame 0 starts from the zero state: its rows contribute nothing to dW_hh)
-        dw_hh = _mm_nt(dgt[:, k:].contiguous(), hs[1:tb].reshape((tb - 1) * k, hd).t()) if tb > 1 else torch.zeros_like(ctx.w_hh_t.t())
+        dw_hh = _mm_nt(dgt[:, k:], hs[1:tb].reshape((tb - 1) * k, hd).t()) if tb > 1 else torch.zeros_like(ctx.w_hh_t.t())
         db = dgates.sum(0)
         return None, dx, None, dw_ih, dw_hh, db, db
 

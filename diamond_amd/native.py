@@ -48,7 +48,7 @@ class ConvParams(C.Structure):
 class LinearParams(C.Structure):
     _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("A", C.c_void_p), ("lda", C.c_int64),
                 ("W", C.c_void_p), ("ldw", C.c_int64), ("bias", C.c_void_p), ("C", C.c_void_p), ("ldc", C.c_int64),
-                ("accumulate", C.c_int32), ("silu", C.c_int32)]
+                ("accumulate", C.c_int32), ("silu", C.c_int32), ("trans_a", C.c_int32), ("trans_w", C.c_int32)]
 
 
 class GnBwdParams(C.Structure):
@@ -67,7 +67,10 @@ class WgradParams(C.Structure):
 class WgradReduceJob(C.Structure):
     _fields_ = [("partials", C.c_void_p), ("dw", C.c_void_p), ("dbias", C.c_void_p), ("num_wg", C.c_int32), ("NB", C.c_int32),
                 ("NCO", C.c_int32), ("NCI", C.c_int32), ("taps", C.c_int32), ("cin_real", C.c_int32), ("ld_cin", C.c_int32),
-                ("c0", C.c_int32)]
+                ("c0", C.c_int32), ("scale", C.c_void_p), ("kind", C.c_int32), ("reserved", C.c_int32)]
+
+
+REDUCE_WGRAD, REDUCE_COLSUM = 0, 1
 
 
 class PackJob(C.Structure):
@@ -122,7 +125,7 @@ EXPORTS = (
     "dmd_attention_bwd_mfma", "dmd_attention_bwd_workspace_floats",
     "dmd_edm_pack_input", "dmd_cond_embed", "dmd_edm_denoised", "dmd_euler_step", "dmd_heun_step", "dmd_quantize_u8", "dmd_reset_state",
     "dmd_dequant_gather", "dmd_resolve_deaths", "dmd_reset_slots", "dmd_merge_slots", "dmd_merge_slots_bwd", "dmd_nchw_to_nhwc",
-    "dmd_nhwc_to_nchw", "dmd_gn_stats", "dmd_gn_stats_valid", "dmd_maxpool2", "dmd_lstm_pointwise", "dmd_lstm_pointwise_bwd", "dmd_categorical_sample", "dmd_rew_end_loss",
+    "dmd_nhwc_to_nchw", "dmd_gn_stats", "dmd_gn_stats_valid", "dmd_maxpool2", "dmd_lstm_pointwise", "dmd_lstm_pointwise_bwd", "dmd_lambda_returns", "dmd_categorical_sample", "dmd_rew_end_loss",
     "dmd_maxpool2_bwd", "dmd_gn_bwd_workspace_bytes", "dmd_gn_silu_bwd", "dmd_wgrad_workspace_floats", "dmd_conv2d_wgrad", "dmd_wgrad_job", "dmd_wgrad_reduce_jobs",
     "dmd_lowres_chain", "dmd_lowres_chain32", "dmd_last_error", "dmd_abi_version", "dmd_reload_env",
 )
@@ -247,6 +250,8 @@ def declare_signatures(L: C.CDLL) -> None:
     L.dmd_lstm_pointwise.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.dmd_lstm_pointwise_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int, C.c_int, C.c_void_p]
+    L.dmd_lambda_returns.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float,
+                                     C.c_float, C.c_void_p]
     L.dmd_categorical_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.dmd_rew_end_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.dmd_conv_stat_tiles.argtypes = [C.c_int, C.c_int]
@@ -373,19 +378,30 @@ def pad_vector(v: Optional[Tensor], n: int) -> Optional[Tensor]:
 
 
 def linear(a: Tensor, w: Tensor, bias: Optional[Tensor], out: Tensor, accumulate: bool = False, silu: bool = False) -> Tensor:
-    """out[M,N] (+)= a[M,K] @ w[N,K]^T + bias; row strides taken from the tensors."""
+    """out[M,N] (+)= a[M,K] @ w[N,K]^T + bias; strides taken from the tensors.  K-contiguous operands with K a multiple of 16 take
+    the 16-byte-load kernel.  Anything else -- an operand that is the transposed VIEW of a row-major (K, M) / (K, N) matrix, or
+    a K that is no multiple of 16 -- takes the either-storage-order instance, which reads the operands where they are and masks
+    the K tail: bitwise the result on contiguous copies zero-padded to a multiple of 16, without making them."""
     p = LinearParams()
     p.M, p.K = a.shape
     p.N = w.shape[0]
     assert w.shape[1] == p.K and out.shape == (p.M, p.N), (a.shape, w.shape, out.shape)
-    assert a.stride(1) == 1 and w.stride(1) == 1 and out.stride(1) == 1
-    p.A, p.lda = ptr(a), a.stride(0)
-    p.W, p.ldw = ptr(w), w.stride(0)
+    assert out.stride(1) == 1 and a.dtype == w.dtype == out.dtype == torch.float32
+
+    def operand(t: Tensor):
+        if t.stride(1) == 1 or t.shape[1] == 1:
+            return 0, t.stride(0)
+        assert t.stride(0) == 1 or t.shape[0] == 1, f"linear: operand strides {t.stride()}: neither storage order"
+        return 1, t.stride(1)
+
+    p.trans_a, p.lda = operand(a)
+    p.trans_w, p.ldw = operand(w)
+    p.A, p.W = ptr(a), ptr(w)
     p.bias = ptr(bias)
     p.C, p.ldc = ptr(out), out.stride(0)
     p.accumulate, p.silu = int(accumulate), int(silu)
     if PROFILER is not None:
-        PROFILER.annotate(f"linear_mfma_kernel<{'true' if p.K >= 512 else 'false'}>", 2.0 * p.M * p.N * p.K,
+        PROFILER.annotate(f"linear_mfma_kernel<{'true' if (p.K + 15) // 16 * 16 >= 512 else 'false'}>", 2.0 * p.M * p.N * p.K,
                           4.0 * (p.M * p.K + p.N * p.K + p.M * p.N))
     check(lib().dmd_linear(C.byref(p), stream()), "dmd_linear")
     return out

@@ -171,13 +171,19 @@ int dmd_conv2d_naive(const dmd_conv_params* p, dmd_stream_t stream);
  * AdaGroupNorm.linear blocks.py:39,44 (all of a forward batched into one call), cond_proj
  * inner_model.py:31-35, LSTM gates, actor/critic heads actor_critic.py:47-48,73. */
 typedef struct dmd_linear_params {
-  int32_t M, N, K;   /* K multiple of 16 */
+  int32_t M, N, K;   /* any K > 0; K % 16 == 0 with K-contiguous 16-byte-aligned rows: the 16-byte-load kernel */
   const float* A; int64_t lda;
   const float* W; int64_t ldw;
   const float* bias; /* [N] or NULL */
   float* C; int64_t ldc;
   int32_t accumulate; /* 1: C += ... */
   int32_t silu;       /* 1: C = silu(...) */
+  /* Operands in either storage order (the backward's data / weight gradient GEMMs): trans_a = 1: A is given as (K, M) row-major,
+   * lda = the stride between its K rows; trans_w = 1: W is given as (K, N) row-major likewise.  The instance that reads them also
+   * runs K-contiguous operands whose K is no multiple of 16 (the tail is masked: exact zeros) or whose lda / ldw is no multiple
+   * of 4.  The result is BITWISE the plain call on K-contiguous copies zero-padded to K rounded up to 16: same 16-wide
+   * steps, same four MFMAs per step, and the split-K route is chosen by the rounded K. */
+  int32_t trans_a, trans_w;
 } dmd_linear_params;
 int dmd_linear(const dmd_linear_params* p, dmd_stream_t stream);
 
@@ -448,6 +454,11 @@ int dmd_lstm_pointwise(const float* gates, const float* c_prev, float* h, float*
  * (NULL = zero) -> dgates (N, 4*Hd), dc_prev (N, Hd)   (autograd of nn.LSTMCell, actor_critic.py:46,72) */
 int dmd_lstm_pointwise_bwd(const float* gates, const float* c_prev, const float* c_new, const float* dh, const float* dc,
                            float* dgates, float* dc_prev, int N, int Hd, dmd_stream_t stream);
+/* TD(lambda) targets of the actor-critic loss (reference actor_critic.py:116-143), one launch: rew / val_bootstrap / ret are
+ * (B, T) fp32, end / trunc (B, T) int64, all contiguous.  The fp32 operations of the reference's expressions in their order
+ * (no fused multiply-add); gamma, one_minus_lambda (= 1 - lambda formed in double) and lambda are the scalars rounded to fp32. */
+int dmd_lambda_returns(const float* rew, const int64_t* end, const int64_t* trunc, const float* val_bootstrap, float* ret, int B, int T,
+                       float gamma, float one_minus_lambda, float lambda, dmd_stream_t stream);
 
 /* argmax(softmax(logits) / E) with injected exponential draws E == Categorical(logits).sample()
  * (env_loop.py:32, world_model_env.py:103-104). */
@@ -533,7 +544,18 @@ typedef struct dmd_wgrad_reduce_job {
   float* dbias;          /* or NULL */
   int32_t num_wg, NB, NCO, NCI, taps, cin_real; /* filled by dmd_wgrad_job */
   int32_t ld_cin, c0;    /* dmd_wgrad_job: cin_real, 0 */
+  /* DEVICE pointer to one float, or NULL (dmd_wgrad_job: NULL): every element leaves as (float)sum * *scale.  The backward of the
+   * actor-critic encoder runs on a gradient scaled by 2^k and hands its 2^-k here: a power of two, so the result is bitwise the
+   * unscaled reduction followed by a multiplication, without that pass. */
+  const float* scale;
+  /* DMD_REDUCE_WGRAD (dmd_wgrad_job), or DMD_REDUCE_COLSUM: the GroupNorm PARAMETER gradients of a block in the same launch --
+   * partials = the (2, N, C) per-(sample, channel) gradients [dmul; dadd] of dmd_gn_silu_bwd, num_wg = N, cin_real = C, the other
+   * counts unused; dw[c] = sum_n dmul[n][c] (dgamma), dbias[c] = sum_n dadd[n][c] (dbeta), both required.  Order: ascending n,
+   * accumulated in fp64, rounded to fp32 once (then scaled): deterministic, and at least as accurate as an fp32 sum. */
+  int32_t kind, reserved;
 } dmd_wgrad_reduce_job;
+#define DMD_REDUCE_WGRAD 0
+#define DMD_REDUCE_COLSUM 1
 /* The job of dmd_conv2d_wgrad(p, defer_reduce = 1): its pointers are p's (which may still be null -- a deferred call needs only
  * num_wg * (NB * NCO * 256 + NCO * 16) floats of workspace, less than dmd_wgrad_workspace_floats, and the caller may size it from
  * the job before it sets p->workspace and job->partials). */
