@@ -4,10 +4,13 @@
 // The reference gets these from ATen autograd (loss.backward(), trainer.py:366).  Here:
 //   * dgrad  = dmd_conv2d on the flipped/transposed weight (host repacks it) -- no new kernel;
 //   * wgrad  = dmd_conv2d_wgrad below: dW[co][ci][tap] = sum_pixels dy[pix][co] * a[pix + tap][ci]
-//     as a GEMM whose contraction runs over PIXELS, on v_mfma_f32_16x16x4_f32 (exact fp32);
+//     as a GEMM whose contraction runs over PIXELS, on the matrix cores: exact fp32 on v_mfma_f32_16x16x4_f32
+//     (wgrad_kernel), or, where the caller asks for DMD_PRECISION_F16X2 as the training steps do, split-fp16 pairs on
+//     v_mfma_f32_16x16x32_f16 (wgrad_ps_kernel, a producer / consumer pair; DIAMOND_WGRAD_PS=0: wgrad_kernel's SPLIT form);
 //     the conv input a = SiLU(GroupNorm(x)) is RECOMPUTED from x + its statistics while staging
 //     (nothing but x and the pooling argmax is saved by the forward);
-//   * GroupNorm+SiLU backward = two passes (group reductions, then elementwise apply);
+//   * GroupNorm+SiLU backward = group reductions, then an elementwise apply: two launches over 256-pixel tiles, or one
+//     launch with a workgroup per image where an image fits one (dmd_gn_silu_bwd picks; every route gives the same bits);
 //   * MaxPool backward = scatter by the saved argmax.
 #include <stdlib.h>
 #include <string.h>
@@ -58,8 +61,21 @@ extern "C" int dmd_maxpool2_bwd(const float* dpooled, const uint8_t* argmax, flo
 //   dx = rstd * (dxh - mean_g(dxh) - xh * mean_g(dxh * xh)) [+ dskip]          (means over the group)
 //   dmul[n][c] = sum_hw du * xh ; dadd[n][c] = sum_hw du                       (host sums over n for
 //   batch-shared affine parameters)
-// Pass A: grid (T, N), T = ceil(HW / 256): partial group sums (fp64) and per-channel sums.
-// Pass B: elementwise.   Pass C: per-(n, c) reduction of the T channel partials.
+// A thread owns one channel quad and every (256 / (C / 4))-th pixel.  Five pieces, each written once below, make up every
+// kernel: (1) the group statistics to LDS, (2) the thread's channel quad, (3) one pixel quad into the thread's sums, (4) the
+// workgroup's reduction of those sums, (5) one pixel quad of dx.  dmd_gn_silu_bwd (gn_bwd_route) launches
+//   * two passes over tiles of GN_BWD_PIX pixels, grid (T, N), T = ceil(HW / 256), where an image is more than one tile:
+//       pass A, gn_bwd_reduce_kernel: a tile's group sums (fp64) and channel sums -> the workspace;
+//       pass B, gn_bwd_apply_kernel: the tile sums in tile order -> the group means, then dx elementwise; workgroup (0, n)
+//       also sums image n's channel partials into dmul / dadd;
+//     GN_BWD_U = 4 pixels requested per thread and trip where the launch is small (T * N <= 1024), else 1;
+//   * one launch, a workgroup per image, the sums staying in LDS, where an image is one tile (HW <= 256: the 16x16 and 8x8
+//     levels, half of a training step's normalisations): gn_bwd_fused_regs_kernel for at most 256 images (the image stays
+//     in registers between the passes), gn_bwd_fused_kernel for more;
+//   * gn_bwd_fused_kernel at any HW for the general groups (48, 80, 144 ... channels: C / 4 need not divide 256).
+// Every route forms every sum in the same order -- a thread's pixels ascending, the wave, then the four waves, then the tiles
+// -- and computes every element by the same expression: the results are bit-identical (tests/test_simt_kernels.py pins
+// it through DIAMOND_GN_BWD_FUSED, tests/test_gpu_kernels.py the two trip depths).
 // ------------------------------------------------------------------------------------------------
 struct GnBwdElem {
   float xh, du, dxh;
@@ -86,74 +102,71 @@ __device__ __forceinline__ double gn_bwd_count(const dmd_gn_bwd_params& p) { ret
 #define GN_BWD_PIX 256  // pixels per workgroup in passes A and B
 #define GN_BWD_MAXG 8   // C <= 256
 
-template <int GN_BWD_U>  // pixels requested per thread and trip (dmd_gn_silu_bwd picks by launch size)
-__global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const dmd_gn_bwd_params p, int T, double* __restrict__ group_partial,
-                                                            float* __restrict__ chan_partial) {
-  __shared__ float g_mean[GN_BWD_MAXG], g_rstd[GN_BWD_MAXG];
-  __shared__ double red[4][GN_BWD_MAXG][2];
-  __shared__ float cred[256][8];
-  const int t = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
-  const int C = p.C, CQ = C / 4, G = C / DMD_GN_GROUP > 0 ? C / DMD_GN_GROUP : 1;
-  const int gsz = C / G;
+// (1) the statistics of image n's G groups -> LDS, by threads 0 .. G - 1 (cnt: the elements of a group)
+__device__ __forceinline__ void gn_bwd_group_stats(const dmd_gn_bwd_params& p, int n, int G, double cnt, float* g_mean, float* g_rstd) {
+  const int tid = threadIdx.x;
   if (tid < G) {
     float m, r;
-    dmd_finalize_stats(p.norm.stats + ((size_t)(n * G + tid) * p.norm.stat_tiles) * 2, p.norm.stat_tiles,
-                       (double)gsz * gn_bwd_count(p), &m, &r);
+    dmd_finalize_stats(p.norm.stats + ((size_t)(n * G + tid) * p.norm.stat_tiles) * 2, p.norm.stat_tiles, cnt, &m, &r);
     g_mean[tid] = m;
     g_rstd[tid] = r;
   }
-  __syncthreads();
-  const int q = tid % CQ;
-  const int c0 = 4 * q;
-  const int g = c0 / gsz;
-  const float mean = g_mean[g], rstd = g_rstd[g];
-  float mul[4], add[4];
+}
+
+// (2) the thread's channel quad c0 .. c0 + 3 of group g, with that group's statistics and the quad's affine parameters
+struct GnBwdThread {
+  int c0, g;
+  float mean, rstd, mul[4], add[4];
+  bool silu;  // (false: the identity activation)
+};
+__device__ __forceinline__ int gn_bwd_c0(int C) { return 4 * (threadIdx.x % (C / 4)); }
+__device__ __forceinline__ GnBwdThread gn_bwd_thread(const dmd_gn_bwd_params& p, int n, const float* g_mean, const float* g_rstd) {
+  GnBwdThread th;
+  th.c0 = gn_bwd_c0(p.C);
+  th.g = th.c0 / dmd_gn_group_size(p.C);
+  th.mean = g_mean[th.g];
+  th.rstd = g_rstd[th.g];
+  th.silu = p.identity_activation == 0;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    float m = p.norm.mul ? p.norm.mul[(size_t)n * p.norm.mul_stride + c0 + e] : 1.0f;
+    float m = p.norm.mul ? p.norm.mul[(size_t)n * p.norm.mul_stride + th.c0 + e] : 1.0f;
     if (p.norm.mul_plus_one) m = 1.0f + m;
-    mul[e] = m;
-    add[e] = p.norm.add ? p.norm.add[(size_t)n * p.norm.add_stride + c0 + e] : 0.0f;
+    th.mul[e] = m;
+    th.add[e] = p.norm.add ? p.norm.add[(size_t)n * p.norm.add_stride + th.c0 + e] : 0.0f;
   }
+  return th;
+}
+
+// (3) one pixel quad into the thread's sums: s1 / s2 of its group (dxh, dxh * xh), dm / db of its four channels (du * xh, du).
+// KEEP: xv / dv leave as xh / dxh (the register-resident form: pass B neither reloads nor recomputes sigmoid(u))
+struct GnBwdSums {
   double s1 = 0.0, s2 = 0.0;
   float dm[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f};
-  // GN_BWD_U pixels per trip, every request in front of the first use (a thread's pixels in the same order as one at a time: the
-  // same sums, the same bits).  A launch of the denoiser's training step (batch 32: 512 workgroups at 64 x 64, 128 at 32 x 32) has
-  // two waves per SIMD or fewer, one request pair each: 4 requests deep the two passes take 26.8 instead of 28.3 us on average,
-  // the step 7.80 instead of 7.89 ms; the actor-critic's launches (3,840 images: 61k workgroups, the SIMDs full) are 3 % FASTER one
-  // deep -- occupancy already supplies the requests, and the deeper trip's registers cost a wave (profiles/r06n_ab_gn_bwd.txt).
-  // A pixel that does not exist -- beyond the tile, outside the valid extent -- requests the trip's first pixel instead (a
-  // predicated load is a branch, and behind a branch hipcc waits for everything: see wgrad_ps_kernel).
-  const int pix_end = min(p.HW, (t + 1) * GN_BWD_PIX);
-  const int pstride = 256 / CQ;
-  for (int pix0 = t * GN_BWD_PIX + tid / CQ; pix0 < pix_end; pix0 += GN_BWD_U * pstride) {
-    f32x4 xv[GN_BWD_U], dv[GN_BWD_U];
-    bool ok[GN_BWD_U];
+};
+template <bool KEEP = false>
+__device__ __forceinline__ void gn_bwd_accumulate(GnBwdSums& s, const GnBwdThread& th, f32x4& xv, f32x4& dv) {
 #pragma unroll
-    for (int u = 0; u < GN_BWD_U; ++u) {
-      const int pix = pix0 + u * pstride;
-      ok[u] = pix < pix_end && gn_bwd_exists(p, pix);  // outside the valid extent: not part of any sum
-      const size_t off = ((size_t)n * p.HW + (ok[u] ? pix : pix0)) * C + c0;
-      xv[u] = *(const f32x4*)(p.x + off);
-      dv[u] = *(const f32x4*)(p.da + off);
-    }
-#pragma unroll
-    for (int u = 0; u < GN_BWD_U; ++u) {
-      if (!ok[u]) continue;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const GnBwdElem r = gn_bwd_elem(xv[u][e], dv[u][e], mean, rstd, mul[e], add[e], p.identity_activation == 0);
-        s1 += (double)r.dxh;
-        s2 += (double)r.dxh * (double)r.xh;
-        dm[e] += r.du * r.xh;
-        db[e] += r.du;
-      }
+  for (int e = 0; e < 4; ++e) {
+    const GnBwdElem r = gn_bwd_elem(xv[e], dv[e], th.mean, th.rstd, th.mul[e], th.add[e], th.silu);
+    s.s1 += (double)r.dxh;
+    s.s2 += (double)r.dxh * (double)r.xh;
+    s.dm[e] += r.du * r.xh;
+    s.db[e] += r.du;
+    if (KEEP) {
+      xv[e] = r.xh;
+      dv[e] = r.dxh;
     }
   }
+}
+
+// (4) the workgroup's reduction: the threads' sums -> LDS (with the barrier), then the four waves' sums of group gg by one
+// thread, the sums of channel c over the pixel lanes by another
+__device__ __forceinline__ void gn_bwd_sums_to_lds(const GnBwdSums& s, int g, int G, double (*red)[GN_BWD_MAXG][2], float (*cred)[8]) {
+  const int tid = threadIdx.x;
   // group sums: threads of a wave may belong to different groups (C = 64: quads 0-7 / 8-15)
   for (int gg = 0; gg < G; ++gg) {
-    const double a = dmd_wave_sum(g == gg ? s1 : 0.0);
-    const double b = dmd_wave_sum(g == gg ? s2 : 0.0);
+    const double a = dmd_wave_sum(g == gg ? s.s1 : 0.0);
+    const double b = dmd_wave_sum(g == gg ? s.s2 : 0.0);
     if ((tid & 63) == 0) {
       red[tid >> 6][gg][0] = a;
       red[tid >> 6][gg][1] = b;
@@ -161,30 +174,106 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const dmd_gn_bwd_par
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    cred[tid][e] = dm[e];
-    cred[tid][4 + e] = db[e];
+    cred[tid][e] = s.dm[e];
+    cred[tid][4 + e] = s.db[e];
   }
   __syncthreads();
-  if (tid < G) {
-    double a = 0.0, b = 0.0;
-    for (int w = 0; w < 4; ++w) {
-      a += red[w][tid][0];
-      b += red[w][tid][1];
-    }
-    double* o = group_partial + ((size_t)(n * G + tid) * T + t) * 2;
-    o[0] = a;
-    o[1] = b;
+}
+__device__ __forceinline__ void gn_bwd_group_total(const double (*red)[GN_BWD_MAXG][2], int gg, double* s1, double* s2) {
+  double a = 0.0, b = 0.0;
+  for (int w = 0; w < 4; ++w) {
+    a += red[w][gg][0];
+    b += red[w][gg][1];
   }
-  if (tid < C) {  // channel tid: quad tid / 4, element tid % 4; fixed-order sum over the pixel lanes
-    const int qq = tid >> 2, e = tid & 3;
-    float a = 0.f, b = 0.f;
-    for (int l = 0; l < 256 / CQ; ++l) {
-      a += cred[l * CQ + qq][e];
-      b += cred[l * CQ + qq][4 + e];
+  *s1 = a;
+  *s2 = b;
+}
+__device__ __forceinline__ void gn_bwd_chan_total(const float (*cred)[8], int CQ, int c, float* dm, float* db) {
+  const int qq = c >> 2, e = c & 3;  // channel c: quad c / 4, element c % 4; fixed-order sum over the pixel lanes
+  float a = 0.f, b = 0.f;
+  for (int l = 0; l < 256 / CQ; ++l) {
+    a += cred[l * CQ + qq][e];
+    b += cred[l * CQ + qq][4 + e];
+  }
+  *dm = a;
+  *db = b;
+}
+
+// (5) one pixel quad of dx on top of o (the skip gradient, or zero); KEPT: xv / dv are gn_bwd_accumulate<true>'s xh / dxh
+template <bool KEPT = false>
+__device__ __forceinline__ f32x4 gn_bwd_dx(f32x4 o, const GnBwdThread& th, float m1, float m2, const f32x4& xv, const f32x4& dv) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float xh = xv[e], dxh = dv[e];
+    if (!KEPT) {
+      const GnBwdElem r = gn_bwd_elem(xv[e], dv[e], th.mean, th.rstd, th.mul[e], th.add[e], th.silu);
+      xh = r.xh;
+      dxh = r.dxh;
     }
+    o[e] += th.rstd * (dxh - m1 - xh * m2);
+  }
+  return o;
+}
+
+// One trip of passes A and B over a tile: GN_BWD_U pixels per thread, every request in front of the first use (a thread's pixels
+// in the same order as one at a time: the same sums, the same bits).  A launch of the denoiser's training step (batch 32: 512
+// workgroups at 64 x 64, 128 at 32 x 32) has two waves per SIMD or fewer, one request pair each: 4 requests deep the two passes
+// take 26.8 instead of 28.3 us on average, the step 7.80 instead of 7.89 ms; the actor-critic's launches (3,840 images: 61k
+// workgroups, the SIMDs full) are 3 % FASTER one deep -- occupancy already supplies the requests, and the deeper trip's registers
+// cost a wave (profiles/r06n_ab_gn_bwd.txt).
+// A pixel that does not exist -- beyond the tile, outside the valid extent -- requests the trip's first pixel instead (a
+// predicated load is a branch, and behind a branch hipcc waits for everything: see wgrad_ps_kernel).
+// SKIP: the skip gradient is requested too (a template parameter: a request under `if (p.dskip)` is a branch as well).
+template <int GN_BWD_U, bool SKIP>
+struct GnBwdTrip {
+  f32x4 xv[GN_BWD_U], dv[GN_BWD_U], sv[SKIP ? GN_BWD_U : 1];
+  bool ok[GN_BWD_U];  // the pixel exists: inside the tile and the valid extent
+};
+template <int GN_BWD_U, bool SKIP>
+__device__ __forceinline__ void gn_bwd_request(GnBwdTrip<GN_BWD_U, SKIP>& r, const dmd_gn_bwd_params& p, int n, int c0, int pix0,
+                                               int pstride, int pix_end) {
+#pragma unroll
+  for (int u = 0; u < GN_BWD_U; ++u) {
+    const int pix = pix0 + u * pstride;
+    r.ok[u] = pix < pix_end && gn_bwd_exists(p, pix);
+    const size_t off = ((size_t)n * p.HW + (r.ok[u] ? pix : pix0)) * p.C + c0;
+    r.xv[u] = *(const f32x4*)(p.x + off);
+    r.dv[u] = *(const f32x4*)(p.da + off);
+    if (SKIP) r.sv[SKIP ? u : 0] = *(const f32x4*)(p.dskip + off);
+  }
+}
+
+template <int GN_BWD_U>  // pixels requested per thread and trip (dmd_gn_silu_bwd picks by launch size)
+__global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const dmd_gn_bwd_params p, int T, double* __restrict__ group_partial,
+                                                            float* __restrict__ chan_partial) {
+  __shared__ float g_mean[GN_BWD_MAXG], g_rstd[GN_BWD_MAXG];
+  __shared__ double red[4][GN_BWD_MAXG][2];
+  __shared__ float cred[256][8];
+  const int t = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
+  const int C = p.C, CQ = C / 4, G = dmd_gn_groups(C);
+  gn_bwd_group_stats(p, n, G, (double)dmd_gn_group_size(C) * gn_bwd_count(p), g_mean, g_rstd);
+  __syncthreads();
+  const GnBwdThread th = gn_bwd_thread(p, n, g_mean, g_rstd);
+  GnBwdSums s;
+  const int pix_end = min(p.HW, (t + 1) * GN_BWD_PIX);
+  const int pstride = 256 / CQ;
+  for (int pix0 = t * GN_BWD_PIX + tid / CQ; pix0 < pix_end; pix0 += GN_BWD_U * pstride) {
+    GnBwdTrip<GN_BWD_U, false> r;
+    gn_bwd_request(r, p, n, th.c0, pix0, pstride, pix_end);
+#pragma unroll
+    for (int u = 0; u < GN_BWD_U; ++u) {
+      if (!r.ok[u]) continue;  // (outside the valid extent: not part of any sum)
+      gn_bwd_accumulate(s, th, r.xv[u], r.dv[u]);
+    }
+  }
+  gn_bwd_sums_to_lds(s, th.g, G, red, cred);
+  if (tid < G) {
+    double* o = group_partial + ((size_t)(n * G + tid) * T + t) * 2;
+    gn_bwd_group_total(red, tid, &o[0], &o[1]);
+  }
+  if (tid < C) {
     float* o = chan_partial + (((size_t)n * T + t) * C + tid) * 2;
-    o[0] = a;
-    o[1] = b;
+    gn_bwd_chan_total(cred, CQ, tid, &o[0], &o[1]);
   }
 }
 
@@ -195,8 +284,8 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const dmd_gn_bwd_para
                                                            const float* __restrict__ chan_partial) {
   __shared__ float g_mean[GN_BWD_MAXG], g_rstd[GN_BWD_MAXG], g_m1[GN_BWD_MAXG], g_m2[GN_BWD_MAXG];
   const int t = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
-  const int C = p.C, CQ = C / 4, G = C / DMD_GN_GROUP > 0 ? C / DMD_GN_GROUP : 1;
-  const int gsz = C / G;
+  const int C = p.C, CQ = C / 4, G = dmd_gn_groups(C);
+  const double cnt = (double)dmd_gn_group_size(C) * gn_bwd_count(p);
   if (t == 0) {
     for (int c = tid; c < C; c += 256) {
       float a = 0.f, b = 0.f;
@@ -209,12 +298,8 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const dmd_gn_bwd_para
       p.dadd[(size_t)n * C + c] = b;
     }
   }
+  gn_bwd_group_stats(p, n, G, cnt, g_mean, g_rstd);
   if (tid < G) {
-    float m, r;
-    const double cnt = (double)gsz * gn_bwd_count(p);
-    dmd_finalize_stats(p.norm.stats + ((size_t)(n * G + tid) * p.norm.stat_tiles) * 2, p.norm.stat_tiles, cnt, &m, &r);
-    g_mean[tid] = m;
-    g_rstd[tid] = r;
     double a = 0.0, b = 0.0;
     const double* gp = group_partial + ((size_t)(n * G + tid) * T) * 2;
     for (int k = 0; k < T; ++k) {
@@ -225,50 +310,26 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const dmd_gn_bwd_para
     g_m2[tid] = (float)(b / cnt);
   }
   __syncthreads();
-  const int q = tid % CQ;
-  const int c0 = 4 * q;
-  const int g = c0 / gsz;
-  const float mean = g_mean[g], rstd = g_rstd[g], m1 = g_m1[g], m2 = g_m2[g];
-  float mul[4], add[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float m = p.norm.mul ? p.norm.mul[(size_t)n * p.norm.mul_stride + c0 + e] : 1.0f;
-    if (p.norm.mul_plus_one) m = 1.0f + m;
-    mul[e] = m;
-    add[e] = p.norm.add ? p.norm.add[(size_t)n * p.norm.add_stride + c0 + e] : 0.0f;
-  }
+  const GnBwdThread th = gn_bwd_thread(p, n, g_mean, g_rstd);
+  const float m1 = g_m1[th.g], m2 = g_m2[th.g];
   const int pix_end = min(p.HW, (t + 1) * GN_BWD_PIX);
   const int pstride = 256 / CQ;
-  // (two copies of the loop, with and without the skip gradient's request: a request under `if (p.dskip)` inside the loop is a branch)
+  // (two copies of the loop, with and without the skip gradient's request: see GnBwdTrip)
   auto pass = [&](auto skip_c) __attribute__((always_inline)) {
     constexpr bool SKIP = decltype(skip_c)::value;
-    for (int pix0 = t * GN_BWD_PIX + tid / CQ; pix0 < pix_end; pix0 += GN_BWD_U * pstride) {  // (GN_BWD_U requests deep: see pass A)
-      f32x4 xv[GN_BWD_U], dv[GN_BWD_U], sv[SKIP ? GN_BWD_U : 1];
-      bool ok[GN_BWD_U];
-#pragma unroll
-      for (int u = 0; u < GN_BWD_U; ++u) {
-        const int pix = pix0 + u * pstride;
-        ok[u] = pix < pix_end && gn_bwd_exists(p, pix);
-        const size_t off = ((size_t)n * p.HW + (ok[u] ? pix : pix0)) * C + c0;
-        xv[u] = *(const f32x4*)(p.x + off);
-        dv[u] = *(const f32x4*)(p.da + off);
-        if (SKIP) sv[SKIP ? u : 0] = *(const f32x4*)(p.dskip + off);
-      }
+    for (int pix0 = t * GN_BWD_PIX + tid / CQ; pix0 < pix_end; pix0 += GN_BWD_U * pstride) {
+      GnBwdTrip<GN_BWD_U, SKIP> r;
+      gn_bwd_request(r, p, n, th.c0, pix0, pstride, pix_end);
 #pragma unroll
       for (int u = 0; u < GN_BWD_U; ++u) {
         const int pix = pix0 + u * pstride;
         if (pix >= pix_end) continue;
-        const size_t off = ((size_t)n * p.HW + pix) * C + c0;
         f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (ok[u]) {  // (outside the valid extent: a zero gradient)
-          if (SKIP) o = sv[SKIP ? u : 0];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const GnBwdElem r = gn_bwd_elem(xv[u][e], dv[u][e], mean, rstd, mul[e], add[e], p.identity_activation == 0);
-            o[e] += rstd * (r.dxh - m1 - r.xh * m2);
-          }
+        if (r.ok[u]) {  // (outside the valid extent: a zero gradient)
+          if (SKIP) o = r.sv[SKIP ? u : 0];
+          o = gn_bwd_dx(o, th, m1, m2, r.xv[u], r.dv[u]);
         }
-        *(f32x4*)(p.dx + off) = o;
+        *(f32x4*)(p.dx + ((size_t)n * p.HW + pix) * C + th.c0) = o;
       }
     }
   };
@@ -278,92 +339,40 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const dmd_gn_bwd_para
     pass(std::false_type{});
 }
 
-// HW <= 256 (the 16x16 and 8x8 levels: half of a training step's normalisations): ONE workgroup holds a whole image, so both
-// passes are one launch -- pass A's sums stay in LDS, nothing goes through the workspace.  Every sum is formed as the two kernels
-// above form it (T = 1: their "sums over tiles" are one term), every element is computed by the same expression: the results
-// are bit-identical to the two launches (DIAMOND_GN_BWD_FUSED=0 takes those: test hook).
-// ANY: C / 4 need not divide 256 (the general groups: C = 48, 80, 144 ...): the threads behind the last whole pixel row of channel
-// quads (256 - (256 / CQ) * CQ of them) take no pixel; the sums are formed as for ANY = false.
-__global__ __launch_bounds__(256) void gn_bwd_fused_kernel(const dmd_gn_bwd_params p) {
-  __shared__ float g_mean[GN_BWD_MAXG], g_rstd[GN_BWD_MAXG], g_m1[GN_BWD_MAXG], g_m2[GN_BWD_MAXG];
-  __shared__ double red[4][GN_BWD_MAXG][2];
-  __shared__ float cred[256][8];
-  const int n = blockIdx.x, tid = threadIdx.x;
-  const int C = p.C, CQ = C / 4, G = C / DMD_GN_GROUP > 0 ? C / DMD_GN_GROUP : 1;
-  const int gsz = C / G;
-  const double cnt = (double)gsz * gn_bwd_count(p);
+// The one-launch forms: ONE workgroup holds a whole image, so pass A's sums stay in LDS and nothing goes through the workspace.
+// Every sum is formed as the two kernels above form it (T = 1: their "sums over tiles" are one term), every element is computed
+// by the same expression: the results are bit-identical to the two launches (DIAMOND_GN_BWD_FUSED=0 takes those: test hook).
+
+// the image's sums (ends behind its barrier): the group means of dxh and dxh * xh -> LDS, the channel sums -> dmul / dadd
+__device__ __forceinline__ void gn_bwd_image_totals(const dmd_gn_bwd_params& p, int n, int G, double cnt, const GnBwdSums& s, int g,
+                                                    double (*red)[GN_BWD_MAXG][2], float (*cred)[8], float* g_m1, float* g_m2) {
+  const int tid = threadIdx.x;
+  gn_bwd_sums_to_lds(s, g, G, red, cred);
   if (tid < G) {
-    float m, r;
-    dmd_finalize_stats(p.norm.stats + ((size_t)(n * G + tid) * p.norm.stat_tiles) * 2, p.norm.stat_tiles, cnt, &m, &r);
-    g_mean[tid] = m;
-    g_rstd[tid] = r;
-  }
-  __syncthreads();
-  const int q = tid % CQ;
-  const int c0 = 4 * q;
-  const int g = c0 / gsz;
-  const float mean = g_mean[g], rstd = g_rstd[g];
-  float mul[4], add[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float m = p.norm.mul ? p.norm.mul[(size_t)n * p.norm.mul_stride + c0 + e] : 1.0f;
-    if (p.norm.mul_plus_one) m = 1.0f + m;
-    mul[e] = m;
-    add[e] = p.norm.add ? p.norm.add[(size_t)n * p.norm.add_stride + c0 + e] : 0.0f;
-  }
-  double s1 = 0.0, s2 = 0.0;
-  float dm[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int pix = tid / CQ; pix < p.HW; pix += 256 / CQ) {
-    if (!gn_bwd_exists(p, pix)) continue;
-    const size_t off = ((size_t)n * p.HW + pix) * C + c0;
-    const f32x4 xv = *(const f32x4*)(p.x + off);
-    const f32x4 dv = *(const f32x4*)(p.da + off);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const GnBwdElem r = gn_bwd_elem(xv[e], dv[e], mean, rstd, mul[e], add[e], p.identity_activation == 0);
-      s1 += (double)r.dxh;
-      s2 += (double)r.dxh * (double)r.xh;
-      dm[e] += r.du * r.xh;
-      db[e] += r.du;
-    }
-  }
-  for (int gg = 0; gg < G; ++gg) {
-    const double a = dmd_wave_sum(g == gg ? s1 : 0.0);
-    const double b = dmd_wave_sum(g == gg ? s2 : 0.0);
-    if ((tid & 63) == 0) {
-      red[tid >> 6][gg][0] = a;
-      red[tid >> 6][gg][1] = b;
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    cred[tid][e] = dm[e];
-    cred[tid][4 + e] = db[e];
-  }
-  __syncthreads();
-  if (tid < G) {
-    double a = 0.0, b = 0.0;
-    for (int w = 0; w < 4; ++w) {
-      a += red[w][tid][0];
-      b += red[w][tid][1];
-    }
+    double a, b;
+    gn_bwd_group_total(red, tid, &a, &b);
     g_m1[tid] = (float)(a / cnt);
     g_m2[tid] = (float)(b / cnt);
   }
-  if (tid < C) {
-    const int qq = tid >> 2, e = tid & 3;
-    float a = 0.f, b = 0.f;
-    for (int l = 0; l < 256 / CQ; ++l) {
-      a += cred[l * CQ + qq][e];
-      b += cred[l * CQ + qq][4 + e];
-    }
-    p.dmul[(size_t)n * C + tid] = a;
-    p.dadd[(size_t)n * C + tid] = b;
-  }
+  if (tid < p.C) gn_bwd_chan_total(cred, p.C / 4, tid, &p.dmul[(size_t)n * p.C + tid], &p.dadd[(size_t)n * p.C + tid]);
   __syncthreads();
-  const float m1 = g_m1[g], m2 = g_m2[g];
-  for (int pix = tid / CQ; pix < p.HW; pix += 256 / CQ) {
-    const size_t off = ((size_t)n * p.HW + pix) * C + c0;
+}
+
+// passes A and B of a thread over the image in memory: pixels pix_first, pix_first + lanes ...
+__device__ __forceinline__ void gn_bwd_image_sums(GnBwdSums& s, const dmd_gn_bwd_params& p, int n, const GnBwdThread& th, int pix_first,
+                                                  int lanes) {
+  for (int pix = pix_first; pix < p.HW; pix += lanes) {
+    if (!gn_bwd_exists(p, pix)) continue;
+    const size_t off = ((size_t)n * p.HW + pix) * p.C + th.c0;
+    f32x4 xv = *(const f32x4*)(p.x + off);
+    f32x4 dv = *(const f32x4*)(p.da + off);
+    gn_bwd_accumulate(s, th, xv, dv);
+  }
+}
+__device__ __forceinline__ void gn_bwd_image_apply(const dmd_gn_bwd_params& p, int n, const GnBwdThread& th, float m1, float m2,
+                                                   int pix_first, int lanes) {
+  for (int pix = pix_first; pix < p.HW; pix += lanes) {
+    const size_t off = ((size_t)n * p.HW + pix) * p.C + th.c0;
     if (!gn_bwd_exists(p, pix)) {
       *(f32x4*)(p.dx + off) = (f32x4){0.f, 0.f, 0.f, 0.f};
       continue;
@@ -372,133 +381,55 @@ __global__ __launch_bounds__(256) void gn_bwd_fused_kernel(const dmd_gn_bwd_para
     const f32x4 dv = *(const f32x4*)(p.da + off);
     f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (p.dskip) o = *(const f32x4*)(p.dskip + off);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const GnBwdElem r = gn_bwd_elem(xv[e], dv[e], mean, rstd, mul[e], add[e], p.identity_activation == 0);
-      o[e] += rstd * (r.dxh - m1 - r.xh * m2);
-    }
-    *(f32x4*)(p.dx + off) = o;
+    *(f32x4*)(p.dx + off) = gn_bwd_dx(o, th, m1, m2, xv, dv);
   }
 }
 
-// gn_bwd_fused_kernel for every width the grouping rule allows up to 256 channels (dmd_gn_width_ok: the general groups of 48, 80,
-// 144 ... channels, where C / 4 need not divide 256), any HW, one workgroup per image: the threads behind the last whole row of
-// channel quads (256 - (256 / CQ) * CQ of them) take no pixel; everything else as there.
-__global__ __launch_bounds__(256) void gn_bwd_any_kernel(const dmd_gn_bwd_params p) {
+// Every width the grouping rule allows up to 256 channels (dmd_gn_width_ok), any HW.  Where C / 4 does not divide 256 (the general
+// groups of 48, 80, 144 ... channels) the threads behind the last whole row of channel quads (256 - (256 / CQ) * CQ of them) take
+// no pixel; the sums are formed as everywhere else.
+// At most SIX waves per SIMD: with thousands of images a pass-B read finds its image in the cache only while few enough
+// workgroups are resident -- 3,840 images of 16 x 16 x 64 take 255 us at six waves, 276 at seven, 280 at eight, and the general
+// widths are as fast or faster at six (48 channels 189 against 196 us, 80 channels 351 against 377:
+// profiles/gn_bwd_one_body.txt).  The body needs about 56 registers, so without the bound hipcc would allow eight.
+#ifdef __HIP__
+#define GN_BWD_MAX_WAVES(n) __attribute__((amdgpu_waves_per_eu(1, n)))
+#else  // (tests/simt compiles this source for the host, which has no such attribute)
+#define GN_BWD_MAX_WAVES(n)
+#endif
+__global__ __launch_bounds__(256) GN_BWD_MAX_WAVES(6) void gn_bwd_fused_kernel(const dmd_gn_bwd_params p) {
   __shared__ float g_mean[GN_BWD_MAXG], g_rstd[GN_BWD_MAXG], g_m1[GN_BWD_MAXG], g_m2[GN_BWD_MAXG];
   __shared__ double red[4][GN_BWD_MAXG][2];
   __shared__ float cred[256][8];
   const int n = blockIdx.x, tid = threadIdx.x;
-  const int C = p.C, CQ = C / 4, G = C / DMD_GN_GROUP > 0 ? C / DMD_GN_GROUP : 1;
-  const int gsz = C / G;
-  const double cnt = (double)gsz * gn_bwd_count(p);
-  if (tid < G) {
-    float m, r;
-    dmd_finalize_stats(p.norm.stats + ((size_t)(n * G + tid) * p.norm.stat_tiles) * 2, p.norm.stat_tiles, cnt, &m, &r);
-    g_mean[tid] = m;
-    g_rstd[tid] = r;
-  }
+  const int C = p.C, CQ = C / 4, G = dmd_gn_groups(C);
+  const double cnt = (double)dmd_gn_group_size(C) * gn_bwd_count(p);
+  gn_bwd_group_stats(p, n, G, cnt, g_mean, g_rstd);
   __syncthreads();
-  const int q = tid % CQ;
-  const int c0 = 4 * q;
-  const int g = c0 / gsz;
+  const GnBwdThread th = gn_bwd_thread(p, n, g_mean, g_rstd);
   const int pix_first = tid < (256 / CQ) * CQ ? tid / CQ : p.HW;
-  const float mean = g_mean[g], rstd = g_rstd[g];
-  float mul[4], add[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float m = p.norm.mul ? p.norm.mul[(size_t)n * p.norm.mul_stride + c0 + e] : 1.0f;
-    if (p.norm.mul_plus_one) m = 1.0f + m;
-    mul[e] = m;
-    add[e] = p.norm.add ? p.norm.add[(size_t)n * p.norm.add_stride + c0 + e] : 0.0f;
-  }
-  double s1 = 0.0, s2 = 0.0;
-  float dm[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int pix = pix_first; pix < p.HW; pix += 256 / CQ) {
-    if (!gn_bwd_exists(p, pix)) continue;
-    const size_t off = ((size_t)n * p.HW + pix) * C + c0;
-    const f32x4 xv = *(const f32x4*)(p.x + off);
-    const f32x4 dv = *(const f32x4*)(p.da + off);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const GnBwdElem r = gn_bwd_elem(xv[e], dv[e], mean, rstd, mul[e], add[e], p.identity_activation == 0);
-      s1 += (double)r.dxh;
-      s2 += (double)r.dxh * (double)r.xh;
-      dm[e] += r.du * r.xh;
-      db[e] += r.du;
-    }
-  }
-  for (int gg = 0; gg < G; ++gg) {
-    const double a = dmd_wave_sum(g == gg ? s1 : 0.0);
-    const double b = dmd_wave_sum(g == gg ? s2 : 0.0);
-    if ((tid & 63) == 0) {
-      red[tid >> 6][gg][0] = a;
-      red[tid >> 6][gg][1] = b;
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    cred[tid][e] = dm[e];
-    cred[tid][4 + e] = db[e];
-  }
-  __syncthreads();
-  if (tid < G) {
-    double a = 0.0, b = 0.0;
-    for (int w = 0; w < 4; ++w) {
-      a += red[w][tid][0];
-      b += red[w][tid][1];
-    }
-    g_m1[tid] = (float)(a / cnt);
-    g_m2[tid] = (float)(b / cnt);
-  }
-  if (tid < C) {
-    const int qq = tid >> 2, e = tid & 3;
-    float a = 0.f, b = 0.f;
-    for (int l = 0; l < 256 / CQ; ++l) {
-      a += cred[l * CQ + qq][e];
-      b += cred[l * CQ + qq][4 + e];
-    }
-    p.dmul[(size_t)n * C + tid] = a;
-    p.dadd[(size_t)n * C + tid] = b;
-  }
-  __syncthreads();
-  const float m1 = g_m1[g], m2 = g_m2[g];
-  for (int pix = pix_first; pix < p.HW; pix += 256 / CQ) {
-    const size_t off = ((size_t)n * p.HW + pix) * C + c0;
-    if (!gn_bwd_exists(p, pix)) {
-      *(f32x4*)(p.dx + off) = (f32x4){0.f, 0.f, 0.f, 0.f};
-      continue;
-    }
-    const f32x4 xv = *(const f32x4*)(p.x + off);
-    const f32x4 dv = *(const f32x4*)(p.da + off);
-    f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (p.dskip) o = *(const f32x4*)(p.dskip + off);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const GnBwdElem r = gn_bwd_elem(xv[e], dv[e], mean, rstd, mul[e], add[e], p.identity_activation == 0);
-      o[e] += rstd * (r.dxh - m1 - r.xh * m2);
-    }
-    *(f32x4*)(p.dx + off) = o;
-  }
+  GnBwdSums s;
+  gn_bwd_image_sums(s, p, n, th, pix_first, 256 / CQ);
+  gn_bwd_image_totals(p, n, G, cnt, s, th.g, red, cred, g_m1, g_m2);
+  gn_bwd_image_apply(p, n, th, g_m1[th.g], g_m2[th.g], pix_first, 256 / CQ);
 }
 
-// Round 6, for launches of at most one workgroup per CU (the denoiser training step's batch of 32: a launch is 32 workgroups and
-// their latency, 14.7 us): the image stays in REGISTERS between the two passes (at most GN_FUSED_ITEMS float4 pairs per thread, requested up
-// front: a workgroup per image is one wave of loads, not 16 dependent round trips, and pass B neither reloads nor recomputes
-// sigmoid(u)); images with more items per thread (C = 128 at 16 x 16) take the two loops of round 4.  Same sums in the same order.  It
-// needs every register of a SIMD (one workgroup per CU): launches of more images (the actor-critic backward: 3,840) stay on
-// gn_bwd_fused_kernel above, which measured 259 us where this one takes 352 (tools/wgrad_bench.py gn, 16 x 16 x 64 channels).
+// For launches of at most one workgroup per CU (the denoiser training step's batch of 32: a launch is 32 workgroups and their
+// latency, 14.7 us): the image stays in REGISTERS between the two passes (at most GN_FUSED_ITEMS float4 pairs per thread,
+// requested up front: a workgroup per image is one wave of loads, not 16 dependent round trips, and pass B neither reloads nor
+// recomputes sigmoid(u)); images with more items per thread (C = 128 at 16 x 16) take gn_bwd_fused_kernel's two loops.  Same
+// sums in the same order.  It needs every register of a SIMD (one workgroup per CU): launches of more images (the actor-critic
+// backward: 3,840) stay on gn_bwd_fused_kernel above, which measured 259 us where this one takes 352 (tools/wgrad_bench.py gn,
+// 16 x 16 x 64 channels).
 #define GN_FUSED_ITEMS 16
 __global__ __launch_bounds__(256) void gn_bwd_fused_regs_kernel(const dmd_gn_bwd_params p) {
   __shared__ float g_mean[GN_BWD_MAXG], g_rstd[GN_BWD_MAXG], g_m1[GN_BWD_MAXG], g_m2[GN_BWD_MAXG];
   __shared__ double red[4][GN_BWD_MAXG][2];
   __shared__ float cred[256][8];
   const int n = blockIdx.x, tid = threadIdx.x;
-  const int C = p.C, CQ = C / 4, G = C / DMD_GN_GROUP > 0 ? C / DMD_GN_GROUP : 1;
-  const int gsz = C / G;
-  const double cnt = (double)gsz * gn_bwd_count(p);
-  const int q = tid % CQ;
-  const int c0 = 4 * q;
+  const int C = p.C, CQ = C / 4, G = dmd_gn_groups(C);
+  const double cnt = (double)dmd_gn_group_size(C) * gn_bwd_count(p);
+  const int c0 = gn_bwd_c0(C);
   const int lanes = 256 / CQ;  // pixels per round
   const bool in_regs = p.HW <= GN_FUSED_ITEMS * lanes;  // uniform
   // ---- every request of the image first (unconditional: an item behind the image re-reads its last pixel, unused) ----
@@ -512,92 +443,22 @@ __global__ __launch_bounds__(256) void gn_bwd_fused_regs_kernel(const dmd_gn_bwd
       dr[it] = *(const f32x4*)(p.da + off);
     }
   }
-  if (tid < G) {
-    float m, r;
-    dmd_finalize_stats(p.norm.stats + ((size_t)(n * G + tid) * p.norm.stat_tiles) * 2, p.norm.stat_tiles, cnt, &m, &r);
-    g_mean[tid] = m;
-    g_rstd[tid] = r;
-  }
+  gn_bwd_group_stats(p, n, G, cnt, g_mean, g_rstd);
   __syncthreads();
-  const int g = c0 / gsz;
-  const float mean = g_mean[g], rstd = g_rstd[g];
-  float mul[4], add[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float m = p.norm.mul ? p.norm.mul[(size_t)n * p.norm.mul_stride + c0 + e] : 1.0f;
-    if (p.norm.mul_plus_one) m = 1.0f + m;
-    mul[e] = m;
-    add[e] = p.norm.add ? p.norm.add[(size_t)n * p.norm.add_stride + c0 + e] : 0.0f;
-  }
-  double s1 = 0.0, s2 = 0.0;
-  float dm[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f};
+  const GnBwdThread th = gn_bwd_thread(p, n, g_mean, g_rstd);
+  GnBwdSums s;
   if (in_regs) {
 #pragma unroll
     for (int it = 0; it < GN_FUSED_ITEMS; ++it) {
       const int pix = tid / CQ + it * lanes;
       if (pix >= p.HW || !gn_bwd_exists(p, pix)) continue;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const GnBwdElem r = gn_bwd_elem(xr[it][e], dr[it][e], mean, rstd, mul[e], add[e], p.identity_activation == 0);
-        s1 += (double)r.dxh;
-        s2 += (double)r.dxh * (double)r.xh;
-        dm[e] += r.du * r.xh;
-        db[e] += r.du;
-        xr[it][e] = r.xh;   // (kept for pass B: the normalised value and the gradient through the activation)
-        dr[it][e] = r.dxh;
-      }
+      gn_bwd_accumulate<true>(s, th, xr[it], dr[it]);  // (xr / dr: xh / dxh from here on)
     }
   } else {
-    for (int pix = tid / CQ; pix < p.HW; pix += lanes) {
-      if (!gn_bwd_exists(p, pix)) continue;
-      const size_t off = ((size_t)n * p.HW + pix) * C + c0;
-      const f32x4 xv = *(const f32x4*)(p.x + off);
-      const f32x4 dv = *(const f32x4*)(p.da + off);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const GnBwdElem r = gn_bwd_elem(xv[e], dv[e], mean, rstd, mul[e], add[e], p.identity_activation == 0);
-        s1 += (double)r.dxh;
-        s2 += (double)r.dxh * (double)r.xh;
-        dm[e] += r.du * r.xh;
-        db[e] += r.du;
-      }
-    }
+    gn_bwd_image_sums(s, p, n, th, tid / CQ, lanes);
   }
-  for (int gg = 0; gg < G; ++gg) {
-    const double a = dmd_wave_sum(g == gg ? s1 : 0.0);
-    const double b = dmd_wave_sum(g == gg ? s2 : 0.0);
-    if ((tid & 63) == 0) {
-      red[tid >> 6][gg][0] = a;
-      red[tid >> 6][gg][1] = b;
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    cred[tid][e] = dm[e];
-    cred[tid][4 + e] = db[e];
-  }
-  __syncthreads();
-  if (tid < G) {
-    double a = 0.0, b = 0.0;
-    for (int w = 0; w < 4; ++w) {
-      a += red[w][tid][0];
-      b += red[w][tid][1];
-    }
-    g_m1[tid] = (float)(a / cnt);
-    g_m2[tid] = (float)(b / cnt);
-  }
-  if (tid < C) {
-    const int qq = tid >> 2, e = tid & 3;
-    float a = 0.f, b = 0.f;
-    for (int l = 0; l < 256 / CQ; ++l) {
-      a += cred[l * CQ + qq][e];
-      b += cred[l * CQ + qq][4 + e];
-    }
-    p.dmul[(size_t)n * C + tid] = a;
-    p.dadd[(size_t)n * C + tid] = b;
-  }
-  __syncthreads();
-  const float m1 = g_m1[g], m2 = g_m2[g];
+  gn_bwd_image_totals(p, n, G, cnt, s, th.g, red, cred, g_m1, g_m2);
+  const float m1 = g_m1[th.g], m2 = g_m2[th.g];
   if (in_regs) {
 #pragma unroll
     for (int it = 0; it < GN_FUSED_ITEMS; ++it) {
@@ -607,38 +468,35 @@ __global__ __launch_bounds__(256) void gn_bwd_fused_regs_kernel(const dmd_gn_bwd
       f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
       if (gn_bwd_exists(p, pix)) {
         if (p.dskip) o = *(const f32x4*)(p.dskip + off);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] += rstd * (dr[it][e] - m1 - xr[it][e] * m2);
+        o = gn_bwd_dx<true>(o, th, m1, m2, xr[it], dr[it]);
       }
       *(f32x4*)(p.dx + off) = o;
     }
     return;
   }
-  for (int pix = tid / CQ; pix < p.HW; pix += lanes) {
-    const size_t off = ((size_t)n * p.HW + pix) * C + c0;
-    if (!gn_bwd_exists(p, pix)) {
-      *(f32x4*)(p.dx + off) = (f32x4){0.f, 0.f, 0.f, 0.f};
-      continue;
-    }
-    const f32x4 xv = *(const f32x4*)(p.x + off);
-    const f32x4 dv = *(const f32x4*)(p.da + off);
-    f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (p.dskip) o = *(const f32x4*)(p.dskip + off);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const GnBwdElem r = gn_bwd_elem(xv[e], dv[e], mean, rstd, mul[e], add[e], p.identity_activation == 0);
-      o[e] += rstd * (r.dxh - m1 - r.xh * m2);
-    }
-    *(f32x4*)(p.dx + off) = o;
-  }
+  gn_bwd_image_apply(p, n, th, m1, m2, tid / CQ, lanes);
 }
 
 static inline int gn_bwd_tiles(int HW) { return (HW + GN_BWD_PIX - 1) / GN_BWD_PIX; }
 
 extern "C" int64_t dmd_gn_bwd_workspace_bytes(int N, int HW, int C) {
   const int T = gn_bwd_tiles(HW);
-  const int G = C / DMD_GN_GROUP > 0 ? C / DMD_GN_GROUP : 1;
-  return (int64_t)N * G * T * 2 * 8 + (int64_t)N * T * C * 2 * 4;
+  return (int64_t)N * dmd_gn_groups(C) * T * 2 * 8 + (int64_t)N * T * C * 2 * 4;
+}
+
+enum GnBwdRoute { GN_BWD_GENERAL, GN_BWD_FUSED_REGS, GN_BWD_FUSED, GN_BWD_TILES_U4, GN_BWD_TILES_U1 };
+
+static GnBwdRoute gn_bwd_route(int N, int HW, int C) {
+  // the general groups (48, 80, 144 channels ...): one launch, a workgroup per image, at any HW
+  if (256 % (C / 4) != 0 || (C % DMD_GN_GROUP != 0 && C > DMD_GN_GROUP)) return GN_BWD_GENERAL;
+  const int T = gn_bwd_tiles(HW);
+  // (DIAMOND_GN_BWD_FUSED: 0 two launches, 1 by launch size, 2 / 3 always the one / the other single launch -- test hooks:
+  //  all four are bit-identical)
+  static DmdEnvInt fused_env{"DIAMOND_GN_BWD_FUSED", 1};
+  const int fused = fused_env.get();
+  if (T == 1 && fused != 0) return fused == 3 || (fused != 2 && N <= 256) ? GN_BWD_FUSED_REGS : GN_BWD_FUSED;
+  // (at most four workgroups per CU: the requests have to come from inside a thread)
+  return (long long)T * N <= 1024 ? GN_BWD_TILES_U4 : GN_BWD_TILES_U1;
 }
 
 extern "C" int dmd_gn_silu_bwd(const dmd_gn_bwd_params* pp, dmd_stream_t stream) {
@@ -650,34 +508,26 @@ extern "C" int dmd_gn_silu_bwd(const dmd_gn_bwd_params* pp, dmd_stream_t stream)
   DMD_CHECK_ARG((pp->C <= 256 && dmd_gn_width_ok(pp->C)) || (pp->C % 4 == 0 && pp->C < DMD_GN_GROUP && 256 % (pp->C / 4) == 0),
                 "gn_silu_bwd: unsupported C %d", pp->C);
   dmd_gn_bwd_params p = *pp;
-  if (256 % (p.C / 4) != 0 || (p.C % DMD_GN_GROUP != 0 && p.C > DMD_GN_GROUP)) {
-    // the general groups (48, 80, 144 channels ...): one launch, a workgroup per image
-    hipLaunchKernelGGL(gn_bwd_any_kernel, dim3(p.N), dim3(256), 0, (hipStream_t)stream, p);
-    DMD_LAUNCH_CHECK();
-    return 0;
-  }
   const int T = gn_bwd_tiles(p.HW);
-  const int G = p.C / DMD_GN_GROUP > 0 ? p.C / DMD_GN_GROUP : 1;
   double* group_partial = (double*)p.workspace;
-  float* chan_partial = (float*)((char*)p.workspace + (size_t)p.N * G * T * 2 * 8);
+  float* chan_partial = (float*)((char*)p.workspace + (size_t)p.N * dmd_gn_groups(p.C) * T * 2 * 8);
   hipStream_t st = (hipStream_t)stream;
-  static DmdEnvInt fused_env{"DIAMOND_GN_BWD_FUSED", 1};
-  if (T == 1 && fused_env.get() != 0) {
-    // (DIAMOND_GN_BWD_FUSED: 0 two launches, 1 by launch size, 2 / 3 always the one / the other single launch -- test hooks:
-    //  all four are bit-identical)
-    if (fused_env.get() == 3 || (fused_env.get() != 2 && p.N <= 256))
-      hipLaunchKernelGGL(gn_bwd_fused_regs_kernel, dim3(p.N), dim3(256), 0, st, p);
-    else
+  switch (gn_bwd_route(p.N, p.HW, p.C)) {
+    case GN_BWD_GENERAL:
+    case GN_BWD_FUSED:
       hipLaunchKernelGGL(gn_bwd_fused_kernel, dim3(p.N), dim3(256), 0, st, p);
-    DMD_LAUNCH_CHECK();
-    return 0;
-  }
-  if ((long long)T * p.N <= 1024) {  // (at most four workgroups per CU: the requests have to come from inside a thread)
-    hipLaunchKernelGGL(gn_bwd_reduce_kernel<4>, dim3(T, p.N), dim3(256), 0, st, p, T, group_partial, chan_partial);
-    hipLaunchKernelGGL(gn_bwd_apply_kernel<4>, dim3(T, p.N), dim3(256), 0, st, p, T, (const double*)group_partial, (const float*)chan_partial);
-  } else {
-    hipLaunchKernelGGL(gn_bwd_reduce_kernel<1>, dim3(T, p.N), dim3(256), 0, st, p, T, group_partial, chan_partial);
-    hipLaunchKernelGGL(gn_bwd_apply_kernel<1>, dim3(T, p.N), dim3(256), 0, st, p, T, (const double*)group_partial, (const float*)chan_partial);
+      break;
+    case GN_BWD_FUSED_REGS:
+      hipLaunchKernelGGL(gn_bwd_fused_regs_kernel, dim3(p.N), dim3(256), 0, st, p);
+      break;
+    case GN_BWD_TILES_U4:
+      hipLaunchKernelGGL(gn_bwd_reduce_kernel<4>, dim3(T, p.N), dim3(256), 0, st, p, T, group_partial, chan_partial);
+      hipLaunchKernelGGL(gn_bwd_apply_kernel<4>, dim3(T, p.N), dim3(256), 0, st, p, T, (const double*)group_partial, (const float*)chan_partial);
+      break;
+    case GN_BWD_TILES_U1:
+      hipLaunchKernelGGL(gn_bwd_reduce_kernel<1>, dim3(T, p.N), dim3(256), 0, st, p, T, group_partial, chan_partial);
+      hipLaunchKernelGGL(gn_bwd_apply_kernel<1>, dim3(T, p.N), dim3(256), 0, st, p, T, (const double*)group_partial, (const float*)chan_partial);
+      break;
   }
   DMD_LAUNCH_CHECK();
   return 0;

@@ -496,6 +496,43 @@ def test_gn_silu_bwd(n, c, h, w, skip):
     assert rel_err(dadd.sum(0), beta.grad) < 2e-5
 
 
+def test_gn_silu_bwd_trip_depths_are_bitwise_equal():
+    """The two launches request four pixels per thread and trip for a small launch (T * N <= 1024) and one for a large one: an
+    image's result does not depend on the batch around it, so the first images of a large batch run alone must give the same
+    bits.  15 x 20 buffer (HW = 300: two tiles, the second partial), 13 x 17 valid, a skip gradient."""
+    from diamond_amd import engine as E, grad_ops as G
+    from tests.test_gpu_valid_extent import _embed
+
+    g = torch.Generator().manual_seed(513)
+    n, few, c, (vh, vw), (hp, wp) = 513, 4, 32, (13, 17), (15, 20)  # T * N = 1026: one pixel per trip; 8: four
+    x = torch.randn(n, c, vh, vw, generator=g, dtype=torch.float64) * 1.7 + 0.4
+    gamma = torch.randn(c, generator=g, dtype=torch.float64) * 0.2 + 1
+    beta = torch.randn(c, generator=g, dtype=torch.float64) * 0.2
+    da = torch.randn(n, c, vh, vw, generator=g, dtype=torch.float64)
+    dskip = torch.randn(n, c, vh, vw, generator=g, dtype=torch.float64)
+    xb, dab, dsb = _embed(x.float(), hp, wp), _embed(da.float(), hp, wp, fill=91.0), _embed(dskip.float(), hp, wp, fill=-17.0)
+    spec = E.NormSpec(mul=gamma.float().to(DEV), add=beta.float().to(DEV))
+    dx, (dmul, dadd) = G.gn_bwd(E.gn_stats(xb, (vh, vw)), spec, dab, dsb)
+    dx4, (dmul4, dadd4) = G.gn_bwd(E.gn_stats(xb[:few].contiguous(), (vh, vw)), spec, dab[:few].contiguous(), dsb[:few].contiguous())
+    torch.cuda.synchronize()
+    assert torch.equal(dx[:few], dx4) and torch.equal(dmul[:few], dmul4) and torch.equal(dadd[:few], dadd4)
+    outside = dx.clone()
+    outside[:, :vh, :vw] = 0
+    assert float(outside.abs().max()) == 0.0 and float(dx[:, :vh, :vw].abs().max()) > 0
+    # one image against the closed form in fp64 (C = 32: one group), x and da as the kernel saw them (rounded to fp32)
+    k = n - 1
+    v, d, s = x[k].float().double(), da[k].float().double(), dskip[k].float().double()
+    ga, be = gamma.float().double()[:, None, None], beta.float().double()[:, None, None]
+    xh = (v - v.mean()) / torch.sqrt(v.var(unbiased=False) + 1e-5)
+    u = xh * ga + be
+    sg = torch.sigmoid(u)
+    du = d * (sg * (1 + u * (1 - sg)))
+    dxh = du * ga
+    want = (dxh - dxh.mean() - xh * (dxh * xh).mean()) / torch.sqrt(v.var(unbiased=False) + 1e-5) + s
+    assert rel_err(dx[k, :vh, :vw].permute(2, 0, 1), want) < 2e-5
+    assert rel_err(dmul[k], (du * xh).sum((1, 2))) < 2e-5 and rel_err(dadd[k], du.sum((1, 2))) < 2e-5
+
+
 def test_maxpool_bwd():
     from diamond_amd import ac_native as A, grad_ops as G
 

@@ -1,7 +1,7 @@
 """Normalised widths that are NOT multiples of 32 channels (tests/group_width_configs.py): the reference forms max(1, C // 32)
 GroupNorm groups of C / groups channels (models/blocks.py:27,38) -- 16, 48, 40 and 36 channels at C = 16, 48, 80 and 144 -- and
 its U-Net's up path normalises concatenations whose 32-channel groups straddle the two sources.  The kernels' general-group
-instances (ConvGeomGN, WgradGeomGN, gn_stats_any_kernel, gn_bwd_any_kernel) and the host's materialised concatenation
+instances (ConvGeomGN, WgradGeomGN, gn_stats_any_kernel, gn_bwd_fused_kernel) and the host's materialised concatenation
 (engine.concat) are held against fp64 torch (kernel level) and against fixtures produced by EXECUTING THE REFERENCE on the same
 configurations (tests/golden/make_golden_groups.py -> tests/golden/groups.pt) at the bars of the default configuration's tests.
 

@@ -47,7 +47,9 @@ if what in ("wgrad", "all"):
         print(f"wgrad {name:22s} {us:8.1f} us  {flop/us/1e6:7.1f} TFLOP/s algorithmic   sum {float(dw.double().sum()):+.9e} abs {float(dw.double().abs().sum()):.9e}", flush=True)
         del x, dy, xa
 GN = [("f2 64^2 c64", 32, 64, 64), ("f2 32^2 c64", 32, 32, 64), ("f2 64^2 c128", 32, 64, 128), ("ac 64^2 c32", 3840, 64, 32), ("ac 32^2 c32", 3840, 32, 32),
-      ("ac 16^2 c64", 3840, 16, 64)]
+      ("ac 16^2 c64", 3840, 16, 64),
+      # the one-launch routes: register-resident, its fallback loops (C = 128 at 16 x 16), and a workgroup per image for many images
+      ("f2 16^2 c64", 32, 16, 64), ("f2 16^2 c128", 32, 16, 128), ("f2 8^2 c64", 32, 8, 64), ("ac 8^2 c64", 3840, 8, 64)]
 if what in ("gn", "all"):
     for name, n, h, c in GN:
         if only not in name:
