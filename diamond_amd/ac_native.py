@@ -9,7 +9,8 @@ activations inside the wgrad kernel's staging pass.  Kernel map:
   forward   dmd_conv2d (GN+SiLU prologue, bias + residual epilogue), dmd_maxpool2 (+ stats of the
             pooled tensor for the next GroupNorm)
   backward  (launched through grad_ops.py) dmd_maxpool2_bwd -> dmd_conv2d_wgrad (dW, db) -> dmd_conv2d on the flipped/transposed
-            weight (dgrad) -> dmd_gn_silu_bwd (dx, dgamma, dbeta; adds the skip-branch gradient)
+            weight (dgrad) -> dmd_gn_silu_bwd (dx, dgamma, dbeta; adds the skip-branch gradient); where `obs` requires a
+            gradient, dmd_conv2d_dgrad_input behind conv_in's weight gradient (the image gradient: one launch, else none)
 
 The LSTM cell and the two heads downstream run on dmd_linear / dmd_lstm_pointwise(_bwd): lstm_native.LstmHeadsFn.
 """
@@ -207,11 +208,16 @@ class _EncoderFn(torch.autograd.Function):
                 gn_batch.flush()
             dcur = dx
         wgrad(ctx.x16, nv.PROLOGUE_NONE, None, dcur, 9, ctx.cimg, 0)
+        # the image gradient, only where autograd asks for it (saliency of the policy / value): conv_in's data gradient from the
+        # same dcur, unscaled by the launch (one launch; none when obs requires no gradient: the imagined window's launches stay)
+        d_obs = None
+        if ctx.needs_input_grad[2]:
+            d_obs, _ = G.dgrad_input(Act(dcur, valid=ctx.x16.valid), plan.conv_in, ctx.cimg, want_b=False, post=inv_scale.reshape(1))
         if batch is not None:
             batch.flush()
         if ctx.bundled:
-            return (None, None, None, flat)
-        return (None, None, None, *[g.view(p.shape) for g, p in zip(out, plan.params)])
+            return (None, None, d_obs, flat)
+        return (None, None, d_obs, *[g.view(p.shape) for g, p in zip(out, plan.params)])
 
 
 class _ParamBundleFn(torch.autograd.Function):

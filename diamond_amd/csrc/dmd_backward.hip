@@ -1532,3 +1532,124 @@ extern "C" int dmd_conv2d_wgrad(const dmd_wgrad_params* p, dmd_stream_t stream) 
   DMD_LAUNCH_CHECK();
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// dmd_conv2d_dgrad_input: the data gradient of a network's FIRST 3x3 convolution (stride 1, pad 1), written as the caller's
+// cropped NCHW image gradients (autograd of conv_in: inner_model.py:46, actor_critic.py:105, rew_end_model.py:37).
+//   dx[n, c, y, x] = sum_{co, ky, kx} dy[n, y + 1 - ky, x + 1 - kx, co] * w[co, c, ky, kx]
+// as a GEMM on v_mfma_f32_16x16x4_f32 with exact fp32 operands (dy has no bounded range, and the work is small): rows = 16 input
+// channels (A = the weights, read from the module's OIHW parameter: no packed copy), columns = 16 pixels of an image row
+// (B = dy), contraction over (tap, co) four output channels at a time.
+// Mapping: workgroup (band, n, cg) = rows [8 band, 8 band + 8) of image n, input channels [16 cg, 16 cg + 16); it walks the band in
+// tiles of 8 x 16 pixels, wave v owns rows 2v, 2v + 1 of the tile (two accumulators).  The grid covers the valid extent only.
+// Staging, per tile and chunk of DGI_CK output channels (one chunk up to Cout = 64: the weights are then staged once per
+// workgroup): the weights as [tap][co][c] (a wave's A read is 64 consecutive floats), the dy tile with its one-pixel halo as
+// [pixel][co] with a pixel stride of DGI_CK + 2 floats (a half-wave's B read: banks 2 j + q, all different).  Positions outside
+// the valid extent are staged as ZERO by selection -- whatever the margins hold, NaN included, is never loaded.
+// Order of every sum: chunks ascending, taps ascending, output channels ascending, inside one accumulator: it depends on
+// neither N, the image's position nor the grid; no atomics.
+// ------------------------------------------------------------------------------------------------
+#define DGI_TH 8
+#define DGI_TW 16
+#define DGI_CK 64
+#define DGI_CS (DGI_CK + 2)
+#define DGI_HALO_W (DGI_TW + 2)
+#define DGI_HALO_PIX ((DGI_TH + 2) * DGI_HALO_W)
+#define DGI_W_FLOATS (9 * DGI_CK * 16)
+#define DGI_SMEM_BYTES ((DGI_W_FLOATS + DGI_HALO_PIX * DGI_CS) * 4)
+
+__global__ __launch_bounds__(256) void dgrad_input_kernel(const dmd_dgrad_input_params p) {
+  DMD_DYNAMIC_LDS(float, dgi_smem);
+  float* wl = dgi_smem;                 // [tap][co - co0][c - 16 cg]
+  float* dl = dgi_smem + DGI_W_FLOATS;  // [halo pixel][DGI_CS]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = lane & 15, q = lane >> 4;
+  const int y0 = blockIdx.x * DGI_TH, n = blockIdx.y, c0 = blockIdx.z * 16;
+  const int vh = p.valid_h, vw = p.valid_w;  // (the launcher has resolved 0, 0)
+  const int nchunk = (p.Cout + DGI_CK - 1) / DGI_CK;
+  const int tiles_x = (vw + DGI_TW - 1) / DGI_TW;
+  const float post = p.post ? *p.post : 1.0f;
+  const float dev_scale = p.scale_a ? p.scale_a[(size_t)n * p.stride_a] : 1.0f;
+  for (int tx = 0; tx < tiles_x; ++tx) {
+    const int x0 = tx * DGI_TW;
+    f32x4 acc[2];
+    acc[0] = acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int ch = 0; ch < nchunk; ++ch) {
+      const int co0 = ch * DGI_CK;
+      const int ck = p.Cout - co0 < DGI_CK ? p.Cout - co0 : DGI_CK;  // a multiple of 16
+      __syncthreads();  // (the waves are done with the previous tile / chunk)
+      if (nchunk > 1 || tx == 0) {
+        for (int i = tid; i < 9 * ck * 16; i += 256) {
+          const int c = i & 15, col = (i >> 4) % ck, tap = (i >> 4) / ck;
+          wl[(tap * DGI_CK + col) * 16 + c] = c0 + c < p.cin ? p.w[((size_t)(co0 + col) * p.cin + c0 + c) * 9 + tap] : 0.f;
+        }
+      }
+      const int pairs = ck >> 1;
+      for (int i = tid; i < DGI_HALO_PIX * pairs; i += 256) {
+        const int pr = i % pairs, pix = i / pairs;
+        const int gy = y0 - 1 + pix / DGI_HALO_W, gx = x0 - 1 + pix % DGI_HALO_W;
+        float2 v = {0.f, 0.f};
+        if (gy >= 0 && gy < vh && gx >= 0 && gx < vw) v = *(const float2*)(p.dy + (((size_t)n * p.H + gy) * p.W + gx) * p.Cout + co0 + 2 * pr);
+        *(float2*)(dl + pix * DGI_CS + 2 * pr) = v;
+      }
+      __syncthreads();
+      const int nks = ck >> 2;
+#pragma unroll 1
+      for (int tap = 0; tap < 9; ++tap) {
+        const int ky = tap / 3, kx = tap - 3 * ky;
+        const float* wa = wl + (tap * DGI_CK + q) * 16 + j;
+        const float* d0 = dl + ((2 * wave + 2 - ky) * DGI_HALO_W + (j + 2 - kx)) * DGI_CS + q;
+        const float* d1 = d0 + DGI_HALO_W * DGI_CS;
+        for (int ks = 0; ks < nks; ++ks) {
+          const float a = wa[ks * 64];
+          acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, d0[ks * 4], acc[0], 0, 0, 0);
+          acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, d1[ks * 4], acc[1], 0, 0, 0);
+        }
+      }
+    }
+    // lane (j, q) holds channels c0 + 4 q + r of pixel x0 + j: dx = (sum * post) * s
+    const int x = x0 + j;
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+      const int y = y0 + 2 * wave + rr;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int c = c0 + 4 * q + r;
+        const bool in_a = c < p.c_split;
+        const float s = in_a != (p.swap_scales != 0) ? dev_scale : p.scale_b;
+        const float v = (acc[rr][r] * post) * s;
+        float* dst = in_a ? p.dx_a : p.dx_b;
+        const size_t plane = in_a ? (size_t)n * p.c_split + c : (size_t)n * (p.cin - p.c_split) + (c - p.c_split);
+        if (y < vh && x < vw && c < p.cin && dst) dst[(plane * vh + y) * vw + x] = v;
+      }
+    }
+  }
+}
+
+extern "C" int dmd_conv2d_dgrad_input(const dmd_dgrad_input_params* pp, dmd_stream_t stream) {
+  DMD_CHECK_ARG(pp && pp->dy && pp->w && (pp->dx_a || pp->dx_b), "dgrad_input: null");
+  dmd_dgrad_input_params p = *pp;
+  DMD_CHECK_ARG(p.N > 0 && p.N <= 65535 && p.H > 0 && p.W > 0, "dgrad_input: N %d (1 .. 65535), buffer %d x %d", p.N, p.H, p.W);
+  DMD_CHECK_ARG(p.valid_h >= 0 && p.valid_h <= p.H && p.valid_w >= 0 && p.valid_w <= p.W && (p.valid_h == 0) == (p.valid_w == 0),
+                "dgrad_input: valid extent %d x %d outside the %d x %d buffer", p.valid_h, p.valid_w, p.H, p.W);
+  DMD_CHECK_ARG(p.Cout > 0 && p.Cout % 16 == 0, "dgrad_input: Cout %d must be a multiple of 16", p.Cout);
+  DMD_CHECK_ARG(p.cin >= 1 && p.cin <= 64, "dgrad_input: cin %d outside 1 .. 64 (four groups of 16 channels)", p.cin);
+  DMD_CHECK_ARG(p.c_split >= 0 && p.c_split <= p.cin, "dgrad_input: c_split %d outside 0 .. cin = %d", p.c_split, p.cin);
+  DMD_CHECK_ARG(p.stride_a == 0 || p.stride_a == 1, "dgrad_input: stride_a %d is 0 or 1", p.stride_a);
+  DMD_CHECK_ARG(p.swap_scales == 0 || p.swap_scales == 1, "dgrad_input: swap_scales %d is 0 or 1", p.swap_scales);
+  DMD_CHECK_ARG(((uintptr_t)p.dy & 7) == 0, "dgrad_input: dy must be 8-byte aligned");
+  if (p.valid_h == 0) p.valid_h = p.H, p.valid_w = p.W;
+  static bool attr_set[DMD_MAX_DEVICES] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= DMD_MAX_DEVICES) dev = 0;
+  if (!attr_set[dev]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dgrad_input_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       DGI_SMEM_BYTES);
+    DMD_CHECK_ARG(e == hipSuccess, "dgrad_input: hipFuncSetAttribute(%d bytes): %s", DGI_SMEM_BYTES, hipGetErrorString(e));
+    attr_set[dev] = true;
+  }
+  hipLaunchKernelGGL(dgrad_input_kernel, dim3((p.valid_h + DGI_TH - 1) / DGI_TH, p.N, (p.cin + 15) / 16), dim3(256), DGI_SMEM_BYTES,
+                     (hipStream_t)stream, p);
+  DMD_LAUNCH_CHECK();
+  return 0;
+}

@@ -196,7 +196,11 @@ class Denoiser(nn.Module):
         differentiates around an exact y):
         the U-Net forward runs on the HIP kernels while its launches are recorded, its backward is
         unet_train.UNetTrainFn; the cond vector / FiLM table (three small GEMMs) run on dmd_linear through lstm_native.LinearFn,
-        whose backward is dmd_linear as well (torch autograd only carries the gradient between the nodes)."""
+        whose backward is dmd_linear as well (torch autograd only carries the gradient between the nodes).
+        IMAGE GRADIENTS: also differentiable w.r.t. `noisy_next_obs` and `obs` where they require a gradient (grad mode on):
+        d noisy = c_in[n] * d packed, d obs = d packed / sigma_data, one extra launch in the backward (grad_ops.dgrad_input) and none
+        when neither does.  The conditioners are constants here, as in the training loss: `sigma` receives NO gradient (neither
+        through c_in nor through c_noise), and integer actions have none."""
         import math
         import torch.nn.functional as F
         from . import unet_train as UT
@@ -211,9 +215,13 @@ class Denoiser(nn.Module):
         # sizes off the kernels' tile grid: the VALID EXTENT of a zero-padded buffer, as in compute_model_output; F is cropped back
         # below, so the loss (and its gradient) covers the real pixels only
         hp, wp = E.padded_extent(h, w, im.unet._num_down)
+        # (the packed buffer is built outside autograd; images that require a gradient enter UNetTrainFn as inputs of their own)
         xc, valid = E.pad_to_extent(noisy_next_obs.detach(), hp, wp)
         oc, _ = E.pad_to_extent(obs.detach(), hp, wp)
         xc, oc = xc.contiguous(), oc.contiguous()
+        images = (None, None, None)
+        if torch.is_grad_enabled() and (noisy_next_obs.requires_grad or obs.requires_grad):
+            images = (noisy_next_obs, obs, (cond4[:, 0].contiguous(), 1.0 / float(self.cfg.sigma_data)))
         packed = torch.empty(n, hp, wp, cpad, device=self.device, dtype=torch.float32)
         nv.check(nv.lib().dmd_edm_pack_input(nv.fptr(xc), nv.fptr(oc), nv.fptr(cond4), 4, float(self.cfg.sigma_data), nv.fptr(packed),
                                              n, cx, cobs, hp, wp, cpad, 1, 0, nv.stream()), "dmd_edm_pack_input")
@@ -233,7 +241,7 @@ class Denoiser(nn.Module):
         table = LinearFn.apply(im._cache, cond, w_cat, b_cat)
         if self._train_params is None:
             self._train_params = UT.trainable_unet_params(im)
-        out = UT.UNetTrainFn.apply(im, packed, table, precision or UT.TRAIN_PRECISION, valid, attn_precision, *self._train_params)
+        out = UT.UNetTrainFn.apply(im, packed, table, precision or UT.TRAIN_PRECISION, valid, attn_precision, *images, *self._train_params)
         return out if valid is None else out[:, :, :h, :w]
 
     def forward(self, batch):

@@ -5,6 +5,8 @@ backward of the U-Net and the reward / end encoder (unet_train.py):
   maxpool_bwd     dmd_maxpool2_bwd
   wgrad           dmd_conv2d_wgrad (dW, db; reduced at once, or left to a WgradBatch: dmd_wgrad_reduce_jobs)
   dgrad_weights   the packed weights of the data gradient, which is dmd_conv2d (engine.conv2d) on the flipped / transposed weight
+  dgrad_input     dmd_conv2d_dgrad_input (the data gradient of a network's FIRST convolution as cropped NCHW image gradients; launched
+                  only where autograd asks for an image gradient)
   gn_bwd          dmd_gn_silu_bwd (GroupNorm + FiLM / affine + SiLU or identity)
   pow2_scaled     the 2^k scaling both backward passes run under
   attention_bwd   dmd_attention_bwd / _bwd_valid (one scalar pair of kernels) or, for long token grids, dmd_attention_bwd_mfma
@@ -249,6 +251,41 @@ def wgrad(x: Act, prologue: int, spec: Optional[NormSpec], dy: Tensor, taps: int
     note()
     nv.check(nv.lib().dmd_conv2d_wgrad(C.byref(p), nv.stream()), "dmd_conv2d_wgrad")
     return dw, db
+
+
+def dgrad_input(dy: Act, conv: nn.Conv2d, c_split: int, want_a: bool = True, want_b: bool = True, scale_a: Optional[Tensor] = None,
+                scale_b: float = 1.0, post: Optional[Tensor] = None, swap_scales: bool = False) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """Image gradients behind a network's first convolution (dmd_conv2d_dgrad_input, ONE launch): dy = the gradient of conv's
+    output (NHWC, its valid extent), -> (dx_a (N, c_split, vh, vw), dx_b (N, cin - c_split, vh, vw)), NCHW and cropped to the
+    extent; None for the one not wanted.  dx = (sum * post) * s: post = the one-element 2^-k of a backward that ran under
+    pow2_scaled; s = scale_a[n] (a one- or N-element device tensor) for dx_a and the float scale_b for dx_b -- the other way round
+    with swap_scales.  Reads conv.weight itself (OIHW): no packed copy, nothing for the audit.  Exact fp32 in both precisions."""
+    n, h, w, cout = dy.shape
+    vh, vw = dy.valid if dy.valid is not None else (h, w)
+    cin = conv.in_channels
+    assert conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.out_channels == cout, conv
+    assert 0 <= c_split <= cin and (want_a or want_b) and dy.t.is_contiguous() and dy.t.dtype == torch.float32
+    wt = conv.weight.detach()
+    if wt.dtype != torch.float32 or not wt.is_contiguous():
+        wt = wt.float().contiguous()
+    dev = dy.t.device
+    dx_a = torch.empty(n, c_split, vh, vw, device=dev, dtype=torch.float32) if want_a else None
+    dx_b = torch.empty(n, cin - c_split, vh, vw, device=dev, dtype=torch.float32) if want_b else None
+    p = nv.DgradInputParams()
+    p.N, p.H, p.W, p.valid_h, p.valid_w, p.Cout, p.cin, p.c_split = n, h, w, vh, vw, cout, cin, c_split
+    p.dy, p.w, p.dx_a, p.dx_b = nv.ptr(dy.t), nv.fptr(wt), nv.fptr(dx_a), nv.fptr(dx_b)
+    if scale_a is not None:
+        assert scale_a.numel() in (1, n) and scale_a.dtype == torch.float32 and scale_a.is_contiguous(), (scale_a.shape, scale_a.dtype)
+        p.scale_a, p.stride_a = nv.ptr(scale_a), int(scale_a.numel() == n and n > 1)
+    p.scale_b = float(scale_b)
+    if post is not None:
+        assert post.numel() == 1 and post.dtype == torch.float32
+        p.post = nv.ptr(post)
+    p.swap_scales = int(swap_scales)
+    if nv.PROFILER is not None:  # (the forward convolution's MACs; dy read once, the image gradients written)
+        nv.PROFILER.annotate("dgrad_input_kernel", 2.0 * 9 * cin * cout * n * vh * vw, 4.0 * n * (h * w * cout + vh * vw * cin))
+    nv.check(nv.lib().dmd_conv2d_dgrad_input(C.byref(p), nv.stream()), "dmd_conv2d_dgrad_input")
+    return dx_a, dx_b
 
 
 def _gn_bwd_instance(c: int) -> bool:

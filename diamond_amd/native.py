@@ -73,6 +73,13 @@ class WgradReduceJob(C.Structure):
 REDUCE_WGRAD, REDUCE_COLSUM = 0, 1
 
 
+class DgradInputParams(C.Structure):
+    _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("valid_h", C.c_int32), ("valid_w", C.c_int32), ("Cout", C.c_int32),
+                ("cin", C.c_int32), ("c_split", C.c_int32), ("dy", C.c_void_p), ("w", C.c_void_p), ("dx_a", C.c_void_p), ("dx_b", C.c_void_p),
+                ("scale_a", C.c_void_p), ("stride_a", C.c_int32), ("scale_b", C.c_float), ("post", C.c_void_p), ("swap_scales", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class PackJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("Cout", C.c_int32), ("Cin", C.c_int32), ("k", C.c_int32),
                 ("kind", C.c_int32), ("transposed", C.c_int32), ("c0", C.c_int32), ("c1", C.c_int32), ("CoutPad", C.c_int32),
@@ -127,7 +134,7 @@ EXPORTS = (
     "dmd_dequant_gather", "dmd_resolve_deaths", "dmd_reset_slots", "dmd_merge_slots", "dmd_merge_slots_bwd", "dmd_nchw_to_nhwc",
     "dmd_nhwc_to_nchw", "dmd_gn_stats", "dmd_gn_stats_valid", "dmd_maxpool2", "dmd_lstm_pointwise", "dmd_lstm_pointwise_bwd", "dmd_lambda_returns", "dmd_categorical_sample", "dmd_rew_end_loss",
     "dmd_maxpool2_bwd", "dmd_gn_bwd_workspace_bytes", "dmd_gn_silu_bwd", "dmd_wgrad_workspace_floats", "dmd_conv2d_wgrad", "dmd_wgrad_job", "dmd_wgrad_reduce_jobs",
-    "dmd_lowres_chain", "dmd_lowres_chain32", "dmd_last_error", "dmd_abi_version", "dmd_reload_env",
+    "dmd_conv2d_dgrad_input", "dmd_lowres_chain", "dmd_lowres_chain32", "dmd_last_error", "dmd_abi_version", "dmd_reload_env",
 )
 
 # entry points that launch kernels (everything except queries / packing helpers that bench.py does not time)
@@ -264,6 +271,7 @@ def declare_signatures(L: C.CDLL) -> None:
     L.dmd_conv2d_wgrad.argtypes = [C.POINTER(WgradParams), C.c_void_p]
     L.dmd_wgrad_job.argtypes = [C.POINTER(WgradParams), C.POINTER(WgradReduceJob)]
     L.dmd_wgrad_reduce_jobs.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.dmd_conv2d_dgrad_input.argtypes = [C.POINTER(DgradInputParams), C.c_void_p]
     L.dmd_lowres_chain.argtypes = [C.POINTER(LowresChainParams), C.c_void_p]
     L.dmd_lowres_chain32.argtypes = [C.POINTER(LowresChainParams), C.c_void_p]
 

@@ -207,14 +207,19 @@ class RewEndModel(nn.Module):
         LSTM over the segment, the head and the FiLM-table GEMM: lstm_native.LinearFn / LstmStepFn (dmd_linear forward and
         backward); the action embedding (a gather) is a torch op under autograd.
         segment: the LSTM as ONE autograd node (lstm_native.LstmSegmentFn: one dW_hh GEMM and one bias sum for the segment) on the
-        features in frame-major order; the same kernels per row, the same logits bit for bit."""
+        features in frame-major order; the same kernels per row, the same logits bit for bit.
+        IMAGE GRADIENTS: `obs` and `next_obs` stay attached -- where one of them requires a gradient (grad mode on) the encoder's
+        backward returns both (one extra launch, grad_ops.dgrad_input; none otherwise: the frames of a training batch require none).
+        Integer actions have no gradient."""
         import torch.nn.functional as F
         from . import unet_train as UT
         from .blocks import AdaGroupNorm
         from .lstm_native import LinearFn, LstmStepFn, lstm_segment
 
         b, t, c, h, w = obs.shape
+        # (the encoder's input is built outside autograd; frames that require a gradient enter EncoderTrainFn as inputs of their own)
         x = torch.cat((obs.reshape(b * t, c, h, w), next_obs.reshape(b * t, c, h, w)), dim=1).detach()
+        frames = (obs, next_obs) if torch.is_grad_enabled() and (obs.requires_grad or next_obs.requires_grad) else (None, None)
         # sizes off the kernels' tile grid: the VALID EXTENT of a zero-padded buffer, as in predict_rew_end
         nd = len(self.encoder.downsamples) - 2
         x, valid = self._pad_to_extent(x)
@@ -235,7 +240,7 @@ class RewEndModel(nn.Module):
         def run(tab: Tensor) -> Tensor:
             return self.encoder.run(RunCtx(self._cache, film, tab, precision=precision), x16, valid).t
 
-        feat = UT.EncoderTrainFn.apply(run, self._cache, table, precision, *self._train_params)  # (b t, s, s, e) NHWC
+        feat = UT.EncoderTrainFn.apply(run, self._cache, table, precision, *frames, *self._train_params)  # (b t, s, s, e) NHWC
         if valid is not None:  # the deepest level's part of its buffer: the gradient outside it is zero
             feat = feat[:, :h // 2 ** nd, :w // 2 ** nd]
         hd, e = self.cfg.lstm_dim, self.cfg.channels[-1]

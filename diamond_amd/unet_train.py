@@ -19,13 +19,15 @@ Attention core: grad_ops.attention_bwd (`dmd_attention_bwd`, from ATTN_BWD_MFMA_
 The FiLM table itself (`cond @ W_cat^T + b_cat`), the 256-wide cond MLP and the
 action embedding are a handful of tiny GEMMs: they run as torch ops under ordinary autograd, so the table gradient
 returned here flows on into the 44 AdaGroupNorm linears, `cond_proj` and `act_emb`.
+Image gradients: where autograd asks for one, conv_in's data gradient goes to the caller's images through grad_ops.dgrad_input
+(`dmd_conv2d_dgrad_input`, one launch; UNetTrainFn / EncoderTrainFn take the images as inputs of their own only then).
 Image sizes off the kernels' tile grid record on the VALID EXTENT of a padded buffer (engine.padded_extent): the gradient
 tensors' margins are then unspecified, and every kernel of the walk reads only the extent it is given (data gradients: dy's,
 weight gradients / GroupNorm backward: their source's, attention: `dmd_attention_bwd_valid`).
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 from torch import Tensor, nn
@@ -128,10 +130,13 @@ class _ParamGrads:
 
 
 def backward_tape(tape: List, cache: E.PackCache, d_out: Tensor, table: Tensor, use_f16: bool,
-                  out_nhwc: Optional[Tensor] = None) -> _ParamGrads:
+                  out_nhwc: Optional[Tensor] = None, image_grad: Optional[Callable[[Act, nn.Conv2d], None]] = None) -> _ParamGrads:
     """Walk the recorded launches in reverse; returns the parameter / FiLM-table gradients.
     `out_nhwc` None: the tape ends with the NCHW head convolution (U-Net) and `d_out` is (N, 3, H, W); otherwise
-    `out_nhwc` is the recorded NHWC activation the network returned (an encoder) and `d_out` its gradient."""
+    `out_nhwc` is the recorded NHWC activation the network returned (an encoder) and `d_out` its gradient.
+    `image_grad` (set only where autograd asks for an image gradient): the network input -- the one source recorded with
+    needs_grad=False, conv_in's -- then carries a gradient: image_grad(dy, conv_in) is called with the gradient of conv_in's
+    output on the extent of its source (one grad_ops.dgrad_input launch, the caller's; nothing is launched without it)."""
     grads = _Grads()
     pg = _ParamGrads(table)
     pending_norm: Dict[int, Tensor] = {}  # gradient w.r.t. GN_affine(x) handed over by a residual_norm consumer
@@ -221,6 +226,10 @@ def backward_tape(tape: List, cache: E.PackCache, d_out: Tensor, table: Tensor, 
                     dx, (dmul, dadd) = G.gn_bwd(a, spec, da, grads.pop(a.t), identity)
                     grads.g[_key(a.t)] = dx  # dx already contains the gradient accumulated so far (dskip)
                     pg.norm_terms(spec, dmul, dadd)
+            elif image_grad is not None:  # the network input: the first convolution's data gradient goes to the caller's images
+                assert prologue == nv.PROLOGUE_NONE and rec.stride == 1 and rec.taps == 9 and not rec.upsample and len(rec.srcs) == 1
+                # (a stride-1 convolution's output exists where its source does: what InnerModel.run zero-fills behind it carries none)
+                image_grad(Act(dy_k, valid=a.valid), conv)
             c0 += ci_real
         if batch is not None:
             if id(conv.weight) in pg.by_param:  # a convolution recorded twice: its gradients are ADDED, so they have to exist
@@ -243,9 +252,16 @@ class UNetTrainFn(torch.autograd.Function):
     conv_in / unet / norm_out / conv_out).  valid = (h, w): the image is that part of the zero-padded packed_in
     (InnerModel.run); F is meaningful in [:h, :w] only and the caller crops it (its gradient is zero outside)."""
 
+    IMAGE_ARGS = 6  # position of (noisy, obs) among forward's arguments
+
     @staticmethod
     def forward(ctx, inner, packed_in: Tensor, table: Tensor, precision: str, valid: Optional[Tuple[int, int]],
-                attn_precision: Optional[str], *params: Tensor) -> Tensor:
+                attn_precision: Optional[str], noisy: Optional[Tensor], obs: Optional[Tensor],
+                image_scales: Optional[Tuple[Tensor, float]], *params: Tensor) -> Tensor:
+        """noisy, obs: the images packed_in was built from (Denoiser.model_output_with_grad), handed over ONLY when one of them
+        requires a gradient -- they are then differentiable inputs (their values are not read: packed_in holds them);
+        image_scales = (c_in (N,) device, 1 / sigma_data): d noisy = c_in[n] * d packed[:, cobs:], d obs = d packed[:, :cobs] / sigma_data
+        (dmd_edm_pack_input packs obs first).  None, None, None otherwise: the backward is what it was, launch for launch."""
         assert E.TAPE is None, "nested recording"
         E.TAPE = []
         try:
@@ -255,14 +271,26 @@ class UNetTrainFn(torch.autograd.Function):
             E.TAPE = None
         ctx.inner, ctx.tape, ctx.table, ctx.precision = inner, tape, table.detach(), precision
         ctx.params = params
+        ctx.image_scales, ctx.cx = image_scales, (0 if noisy is None else noisy.shape[1])
         return out
 
     @staticmethod
     def backward(ctx, d_out: Tensor):
-        pg, inv = scaled_backward(ctx.tape, ctx.inner._cache, d_out, ctx.table, use_f16=ctx.precision == "f16x2")
+        need_noisy, need_obs = ctx.needs_input_grad[UNetTrainFn.IMAGE_ARGS:UNetTrainFn.IMAGE_ARGS + 2]
+        images = {}
+        image_grad = None
+        if need_noisy or need_obs:
+            c_in, inv_sd = ctx.image_scales
+
+            def image_grad(dy: Act, conv: nn.Conv2d, inv: Tensor) -> None:
+                # channels [0, cobs) are obs / sigma_data (a host scalar), [cobs, cobs + cx) noisy * c_in[n]: swap_scales
+                images["obs"], images["noisy"] = G.dgrad_input(dy, conv, conv.in_channels - ctx.cx, want_a=need_obs, want_b=need_noisy,
+                                                               scale_a=c_in, scale_b=inv_sd, post=inv.reshape(1), swap_scales=True)
+
+        pg, inv = scaled_backward(ctx.tape, ctx.inner._cache, d_out, ctx.table, use_f16=ctx.precision == "f16x2", image_grad=image_grad)
         ctx.tape = None  # free the saved activations
         grads = _unscale(pg, ctx.params, inv)
-        return (None, None, pg.dtable * inv, None, None, None, *grads)
+        return (None, None, pg.dtable * inv, None, None, None, images.get("noisy"), images.get("obs"), None, *grads)
 
 
 def _unscale(pg: "_ParamGrads", params, inv: Tensor):
@@ -283,19 +311,26 @@ def _unscale(pg: "_ParamGrads", params, inv: Tensor):
 
 
 def scaled_backward(tape: List, cache: E.PackCache, d_out: Tensor, table: Tensor, use_f16: bool,
-                    out_nhwc: Optional[Tensor] = None) -> Tuple[_ParamGrads, Tensor]:
+                    out_nhwc: Optional[Tensor] = None, image_grad=None) -> Tuple[_ParamGrads, Tensor]:
     """backward_tape on d_out * 2^k with the largest entry O(1) (grad_ops.pow2_scaled); returns (gradients of the scaled
-    problem, 2^-k)."""
+    problem, 2^-k).  image_grad(dy, conv_in, 2^-k), or None: backward_tape's, with the factor that unscales its result."""
     d_scaled, inv = G.pow2_scaled(d_out)
-    return backward_tape(tape, cache, d_scaled, table, use_f16, out_nhwc), inv
+    if image_grad is None:
+        return backward_tape(tape, cache, d_scaled, table, use_f16, out_nhwc), inv
+    return backward_tape(tape, cache, d_scaled, table, use_f16, out_nhwc, image_grad=lambda dy, conv: image_grad(dy, conv, inv)), inv
 
 
 class EncoderTrainFn(torch.autograd.Function):
     """feat = encoder.run(x, table) (an AdaGN-ResBlock encoder returning an NHWC activation: RewEndEncoder) with the
     same recorded-tape backward as the U-Net.  `run(table) -> Tensor` executes the forward."""
 
+    IMAGE_ARGS = 4  # position of (frames_a, frames_b) among forward's arguments
+
     @staticmethod
-    def forward(ctx, run, cache: E.PackCache, table: Tensor, precision: str, *params: Tensor) -> Tensor:
+    def forward(ctx, run, cache: E.PackCache, table: Tensor, precision: str, frames_a: Optional[Tensor], frames_b: Optional[Tensor],
+                *params: Tensor) -> Tensor:
+        """frames_a, frames_b: the images whose channel concatenation `run` feeds to conv_in (RewEndModel: obs, next_obs), handed over
+        ONLY when one of them requires a gradient (differentiable inputs whose values are not read); None, None otherwise."""
         assert E.TAPE is None, "nested recording"
         E.TAPE = []
         try:
@@ -304,14 +339,25 @@ class EncoderTrainFn(torch.autograd.Function):
         finally:
             E.TAPE = None
         ctx.cache, ctx.tape, ctx.table, ctx.precision, ctx.out, ctx.params = cache, tape, table.detach(), precision, out, params
+        ctx.frame_shapes = tuple(None if f is None else tuple(f.shape) for f in (frames_a, frames_b))
         return out
 
     @staticmethod
     def backward(ctx, d_out: Tensor):
-        pg, inv = scaled_backward(ctx.tape, ctx.cache, d_out, ctx.table, ctx.precision == "f16x2", out_nhwc=ctx.out)
+        need_a, need_b = ctx.needs_input_grad[EncoderTrainFn.IMAGE_ARGS:EncoderTrainFn.IMAGE_ARGS + 2]
+        images = {}
+        image_grad = None
+        if need_a or need_b:
+            sa, sb = ctx.frame_shapes
+
+            def image_grad(dy: Act, conv: nn.Conv2d, inv: Tensor) -> None:
+                da, db = G.dgrad_input(dy, conv, sa[-3], want_a=need_a, want_b=need_b, post=inv.reshape(1))
+                images["a"], images["b"] = (None if da is None else da.view(sa)), (None if db is None else db.view(sb))
+
+        pg, inv = scaled_backward(ctx.tape, ctx.cache, d_out, ctx.table, ctx.precision == "f16x2", out_nhwc=ctx.out, image_grad=image_grad)
         ctx.tape = ctx.out = None
         grads = _unscale(pg, ctx.params, inv)
-        return (None, None, pg.dtable * inv, None, *grads)
+        return (None, None, pg.dtable * inv, None, images.get("a"), images.get("b"), *grads)
 
 
 def trainable_unet_params(inner) -> List[nn.Parameter]:

@@ -562,6 +562,42 @@ typedef struct dmd_wgrad_reduce_job {
 int dmd_wgrad_job(const dmd_wgrad_params* p, dmd_wgrad_reduce_job* job);
 int dmd_wgrad_reduce_jobs(const dmd_wgrad_reduce_job* jobs, int njobs, dmd_stream_t stream);
 
+/* (ABI v11 addition) Image gradients: the data gradient of a network's FIRST convolution (3x3, stride 1, pad 1: conv_in of the
+ * denoiser, of the actor-critic encoder and of the reward / end encoder), written straight into the caller's cropped NCHW
+ * tensors -- what ATen autograd returns for `torch.autograd.grad(out, image)` in the reference (inner_model.py:46,
+ * denoiser.py:74-77, actor_critic.py:105, rew_end_model.py:37).  ONE launch, no workspace:
+ *   dx[n, c, y, x] = (post * sum_{co, ky, kx} dy[n, y + 1 - ky, x + 1 - kx, co] * w[co, c, ky, kx]) * s(n, c)
+ *       for 0 <= y < valid_h, 0 <= x < valid_w, 0 <= c < cin
+ * dy is the (valid_h, valid_w) extent of an (N, H, W, Cout) buffer (dmd_conv_params: VALID EXTENT; 0, 0 = (H, W); any H, W >= 1):
+ * its margins are never loaded (they may hold NaN) and count as zero, like the pixels outside the buffer.  w is the convolution's
+ * own OIHW (Cout, cin, 3, 3) parameter: no packed copy exists.  Channels [0, c_split) go to dx_a (N, c_split, valid_h, valid_w),
+ * channels [c_split, cin) to dx_b (N, cin - c_split, valid_h, valid_w), both contiguous; either may be NULL (its channels are
+ * then not written), nothing else is written.
+ * ORDER OF THE TWO MULTIPLICATIONS: the sum is multiplied by *post first (the 2^-k of a backward that ran on a gradient scaled by
+ * 2^k: exact, the true gradient of the convolution's input), the product then by s(n, c) (the chain rule of how the caller built
+ * that input from its images): s = scale_a[n * stride_a] for the channels of dx_a and scale_b for those of dx_b; with swap_scales
+ * the other way round (the denoiser packs obs / sigma_data BEFORE noisy * c_in[n]: dmd_edm_pack_input).  NULL post / scale_a = 1.
+ * Cout: any multiple of 16.  1 <= cin <= 64 (16 channels per workgroup).  Exact fp32 operands on v_mfma_f32_16x16x4_f32 with fp32
+ * accumulation, whatever precision the rest of the backward runs in.  No atomics, one fixed summation order: an image's result
+ * depends on that image alone (not on N, its position in the batch or the launch geometry) and is run-to-run bitwise. */
+typedef struct dmd_dgrad_input_params {
+  int32_t N, H, W;          /* dy's buffer                                                    */
+  int32_t valid_h, valid_w; /* 0, 0 = (H, W)                                                  */
+  int32_t Cout;             /* channels of dy = rows of w, a multiple of 16                   */
+  int32_t cin, c_split;     /* w's input channels; the first c_split of them are dx_a's       */
+  const float* dy;          /* NHWC (N, H, W, Cout), 8-byte aligned                           */
+  const float* w;           /* OIHW (Cout, cin, 3, 3)                                         */
+  float* dx_a;              /* NCHW (N, c_split, valid_h, valid_w) or NULL                    */
+  float* dx_b;              /* NCHW (N, cin - c_split, valid_h, valid_w) or NULL              */
+  const float* scale_a;     /* DEVICE, [n * stride_a], or NULL (1)                            */
+  int32_t stride_a;         /* 0 | 1                                                          */
+  float scale_b;            /* host scalar                                                    */
+  const float* post;        /* DEVICE, one float, or NULL (1)                                 */
+  int32_t swap_scales;      /* 1: scale_a applies to dx_b's channels, scale_b to dx_a's       */
+  int32_t reserved;
+} dmd_dgrad_input_params;
+int dmd_conv2d_dgrad_input(const dmd_dgrad_input_params* p, dmd_stream_t stream);
+
 const char* dmd_last_error(void);
 int dmd_abi_version(void);
 /* The library reads its DIAMOND_* switches from the environment once; this makes it read them again (test hook). */
