@@ -915,3 +915,129 @@ extern "C" int dmd_rew_end_loss(const float* logits, const float* rew, const int
   DMD_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- device-resident replay store: a (B, T) training batch out of the uint8 arena in one launch ---------------------------------
+// (reference data/utils.py:12-41 make_segment + collate_segments_to_batch, per sample on the CPU, then an fp32 upload.)
+// HBM-bound: 1 byte read and 4 written per value.  Workgroups are laid over FRAMES -- the T positions of a sample, then its
+// final observation -- so what a frame is (an arena row, the final observation, or zeros) is uniform over the workgroup: the
+// descriptor is read through scalar loads and no lane diverges.  A workgroup covers 256 x W levels:
+//   W = 16  per_frame % 16 == 0: a lane takes FOUR 4-byte words 1 KiB apart -- every load of a wave is 256 contiguous bytes,
+//           every 16-byte store of a wave 1 KiB contiguous, four loads in flight per lane.  (A lane that owns 16 CONSECUTIVE
+//           levels -- one 16-byte load -- would store 16-byte pieces 64 bytes apart, a quarter of each store's segments.)
+//   W = 4   one word per lane;   W = 1  one level per lane: any per_frame, any alignment
+// A padded position stores zeros and loads nothing.  The five small fields have workgroups of their own in the same launch.
+
+// (float)q / 255.0f * 2.0f - 1.0f (data/episode.py:40) with the division as q * fl(1 / 255) plus ONE residual step: three
+// instructions for the ~10 of an fp32 division, in a kernel whose waves all load, then all convert, then all store.  The
+// quotient is the correctly rounded one for every level 0 ... 255 (tests: all 256 levels, bit for bit against the division).
+__device__ __forceinline__ float seg_dequant(uint32_t q) {
+  const float qf = (float)q, rcp = 1.0f / 255.0f;
+  float r = qf * rcp;
+  r = __builtin_fmaf(__builtin_fmaf(-255.0f, r, qf), rcp, r);
+  return r * 2.0f - 1.0f;
+}
+
+__device__ __forceinline__ f32x4 seg_dequant4(uint32_t pk) {
+  f32x4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = seg_dequant((pk >> (8 * e)) & 0xff);
+  return v;
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void segment_gather_kernel(dmd_segment_gather_params p, int64_t units) {
+  // grid (workgroups per frame, T + 2, B), no division anywhere; workgroups are dispatched along a frame, then along the segment:
+  //   y <  T      frame (b, y)          y == T      the sample's final observation
+  //   y == T + 1  the five small fields of the sample's T positions, one lane each -- in workgroups of their own, so that no
+  //               frame wave waits for the act / rew / end / trunc loads before it issues its frame loads
+  const int64_t b = blockIdx.z;
+  const int64_t first = p.seg[b * 4 + 0], start = p.seg[b * 4 + 1], len = p.seg[b * 4 + 2];
+  if ((int)blockIdx.y == p.T + 1) {
+    if (blockIdx.x != 0) return;
+    for (int t = threadIdx.x; t < p.T; t += 256) {
+      const int64_t s = start + t, f = b * p.T + t;
+      const bool valid = s >= 0 && s < len;
+      const int64_t a = valid ? first + s : 0;
+      if (p.out_act) p.out_act[f] = valid ? p.act[a] : 0;
+      if (p.out_rew) p.out_rew[f] = valid ? p.rew[a] : 0.0f;
+      const uint8_t e = (valid && p.out_end) ? p.end[a] : 0, tr = (valid && p.out_trunc) ? p.trunc[a] : 0;
+      if (p.flag_size == 8) {
+        if (p.out_end) ((int64_t*)p.out_end)[f] = e;
+        if (p.out_trunc) ((int64_t*)p.out_trunc)[f] = tr;
+      } else {
+        if (p.out_end) ((uint8_t*)p.out_end)[f] = e;
+        if (p.out_trunc) ((uint8_t*)p.out_trunc)[f] = tr;
+      }
+      if (p.out_mask) p.out_mask[f] = valid ? 1 : 0;
+    }
+    return;
+  }
+  const bool is_final = (int)blockIdx.y == p.T;
+  const int t = is_final ? 0 : (int)blockIdx.y;
+  float* dst = is_final ? p.out_final : p.out_obs;
+  if (!dst) return;
+  dst += (is_final ? b : b * p.T + t) * p.per_frame;
+  const int64_t final_row = p.finals ? p.seg[b * 4 + 3] : -1;
+  const int64_t s = start + t;
+  const uint8_t* src = nullptr;  // nullptr: a frame of zeros
+  if (is_final) {
+    if (final_row >= 0) src = p.finals + final_row * p.per_frame;
+  } else if (s >= 0 && s < len) {
+    src = p.frames + (first + s) * p.per_frame;
+  } else if (p.put_back_final && s == len && t >= 1 && len >= 1 && final_row >= 0 && p.end[first + len - 1] != 0) {
+    src = p.finals + final_row * p.per_frame;
+  }
+  const int64_t chunk = blockIdx.x;  // 256 lanes x W levels
+  if (W == 16) {
+    const int64_t words = units * 4;  // `units` of 16 levels = 4 words each; the chunk's words: chunk * 1024 ... + 1023
+    uint32_t pk[4] = {0u, 0u, 0u, 0u};
+    if (src) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t w = chunk * 1024 + j * 256 + threadIdx.x;
+        if (w < words) pk[j] = *(const uint32_t*)(src + w * 4);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t w = chunk * 1024 + j * 256 + threadIdx.x;
+      if (w < words) *(f32x4*)(dst + w * 4) = src ? seg_dequant4(pk[j]) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+  } else {
+    const int64_t u = chunk * 256 + threadIdx.x;  // this lane's unit of W levels
+    if (u < units) {
+      if (W == 4)
+        *(f32x4*)(dst + u * 4) = src ? seg_dequant4(*(const uint32_t*)(src + u * 4)) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      else
+        dst[u] = src ? seg_dequant(src[u]) : 0.0f;
+    }
+  }
+}
+
+extern "C" int dmd_segment_gather(const dmd_segment_gather_params* pp, dmd_stream_t stream) {
+  DMD_CHECK_ARG(pp, "segment_gather: null parameter block");
+  const dmd_segment_gather_params& p = *pp;
+  DMD_CHECK_ARG(p.frames && p.act && p.rew && p.end && p.trunc && p.seg, "segment_gather: null arena array or descriptor");
+  DMD_CHECK_ARG(p.B >= 0 && p.T >= 1 && p.per_frame >= 1, "segment_gather: B %d, T %d, per_frame %lld", p.B, p.T, (long long)p.per_frame);
+  DMD_CHECK_ARG(p.flag_size == 1 || p.flag_size == 8, "segment_gather: end / trunc elements of %d bytes (1 or 8)", p.flag_size);
+  if (p.B == 0) return 0;
+  const uintptr_t u8_bases = (uintptr_t)p.frames | (uintptr_t)p.finals;
+  const uintptr_t f32_bases = (uintptr_t)p.out_obs | (uintptr_t)p.out_final;
+  const bool words = p.per_frame % 4 == 0 && u8_bases % 4 == 0 && f32_bases % 16 == 0;  // 4-byte loads, 16-byte stores
+  const int W = !words ? 1 : (p.per_frame % 16 == 0 ? 16 : 4);
+  const int64_t units = p.per_frame / W;
+  const int64_t bpf = (units + 255) / 256;
+  DMD_CHECK_ARG(p.B <= 65535 && p.T <= 65533 && bpf * (p.T + 2) * p.B <= 0x7fffffffLL,
+                "segment_gather: B %d, T %d, %lld workgroups per frame: beyond one launch's grid", p.B, p.T, (long long)bpf);
+  // one workgroup per 256 x W levels (a frame of 3 x 64 x 64: three).  Measured at B = 32, T = 20 (tools/replay_bench.py): 10.0 us
+  // per launch; fewer, looping workgroups per frame are slower (two: 13.1 us, one: 12.3 us)
+  const dim3 grid((unsigned)bpf, (unsigned)p.T + 2, (unsigned)p.B), block(256);
+  if (W == 16)
+    hipLaunchKernelGGL(segment_gather_kernel<16>, grid, block, 0, (hipStream_t)stream, p, units);
+  else if (W == 4)
+    hipLaunchKernelGGL(segment_gather_kernel<4>, grid, block, 0, (hipStream_t)stream, p, units);
+  else
+    hipLaunchKernelGGL(segment_gather_kernel<1>, grid, block, 0, (hipStream_t)stream, p, units);
+  DMD_LAUNCH_CHECK();
+  return 0;
+}

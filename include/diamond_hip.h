@@ -424,6 +424,45 @@ typedef struct dmd_reset_slots_params {
 } dmd_reset_slots_params;
 int dmd_reset_slots(const dmd_reset_slots_params* p, dmd_stream_t stream);
 
+/* ---- device-resident replay store: a whole (B, T) training batch gathered from a uint8 arena in ONE launch ---------------------
+ * (additive to ABI v11.)  Replaces the reference's per-sample CPU pipeline (data/dataset.py:47-49 `__getitem__`,
+ * data/utils.py:12-41 `make_segment` / `collate_segments_to_batch`, then an fp32 upload of the batch).
+ * Arena (device): frames (F, per_frame) uint8 levels, act (F) int64, rew (F) fp32, end / trunc (F) uint8, the episodes' steps
+ * back to back; finals (E, per_frame) uint8: the episodes' final observations (may be NULL when there are none).
+ * seg (B, 4) int64 on the device, per sample: first = arena index of the episode's step 0, start = the segment's first step (may
+ * be negative: left padding), len = the episode's length, final_row = row of `finals` or -1.
+ * For sample b, position t, step s = start + t, valid = 0 <= s < len:
+ *   valid:   out_obs[b][t] = (frames[first + s] / 255) * 2 - 1 (the bits of dmd_dequant_gather and of data/episode.py:36-43),
+ *            out_act / out_rew / out_end / out_trunc [b][t] = the arena's values at first + s, out_mask[b][t] = 1
+ *   invalid: exact zeros everywhere, nothing is read (never an out-of-range address), out_mask[b][t] = 0
+ *   put_back_final != 0: at the one position with s == len, t >= 1, end[first + len - 1] != 0 and final_row >= 0, out_obs[b][t]
+ *            is the dequantised final observation instead of zeros (where models/rew_end_model.py:65-69 writes it); the mask stays 0
+ *   out_final[b] = dequantised finals[final_row], or zeros when final_row < 0.
+ * Every out_* may be NULL (not written).  out_end / out_trunc hold flag_size-byte integers: 1 (uint8) or 8 (int64).
+ * Any per_frame >= 1: 16-byte stores where per_frame % 4 == 0, frames / finals are 4-byte and out_obs / out_final 16-byte aligned
+ * (16 levels per lane where per_frame % 16 == 0, else 4); one level per lane otherwise. */
+typedef struct dmd_segment_gather_params {
+  int32_t B, T;
+  int64_t per_frame;       /* C * H * W */
+  int32_t flag_size;       /* bytes per element of out_end / out_trunc: 1 or 8 */
+  int32_t put_back_final;
+  const uint8_t* frames;   /* (F, per_frame) */
+  const int64_t* act;      /* (F) */
+  const float* rew;        /* (F) */
+  const uint8_t* end;      /* (F) */
+  const uint8_t* trunc;    /* (F) */
+  const uint8_t* finals;   /* (E, per_frame) or NULL */
+  const int64_t* seg;      /* (B, 4): first, start, len, final_row */
+  float* out_obs;          /* (B, T, per_frame) */
+  int64_t* out_act;        /* (B, T) */
+  float* out_rew;          /* (B, T) */
+  void* out_end;           /* (B, T) of flag_size bytes */
+  void* out_trunc;         /* (B, T) of flag_size bytes */
+  uint8_t* out_mask;       /* (B, T): mask_padding */
+  float* out_final;        /* (B, per_frame) */
+} dmd_segment_gather_params;
+int dmd_segment_gather(const dmd_segment_gather_params* p, dmd_stream_t stream);
+
 /* out[r] = row_slot[r] >= 0 ? slots[row_slot[r]] : base[r]  (rows of D floats): the burnt-in policy LSTM state of the reset rows
  * merged into the batch's state (env_loop.py:51-56), and the transposed operation for its backward:
  * d_base[r] = row_slot[r] >= 0 ? 0 : d_out[r] (d_base may be NULL);  d_slots[j] = slot_row[j] >= 0 ? d_out[slot_row[j]] : 0 */
