@@ -137,12 +137,17 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ in, float* __restr
 // ---- uint8 frame pool (episode frames are uint8 on disk, data/episode.py:36-50) ----------------
 // u8 = round((x + 1) / 2 * 255) of frames in [-1, 1]; *off_grid is set when a value is not exactly the
 // dequantisation of its level (such a pool must stay fp32).
+// the level of a value in [-1, 1] (values outside are clamped), as a float 0 ... 255
+__device__ __forceinline__ float dmd_level(float v) {
+  const float lv = rintf((v + 1.0f) / 2.0f * 255.0f);
+  return fminf(fmaxf(lv, 0.0f), 255.0f);
+}
+
 __global__ void quantize_u8_kernel(const float* __restrict__ x, uint8_t* __restrict__ q, int* __restrict__ off_grid, int64_t n) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n) return;
   const float v = x[idx];
-  const float lv = rintf((v + 1.0f) / 2.0f * 255.0f);
-  const float lc = fminf(fmaxf(lv, 0.0f), 255.0f);
+  const float lc = dmd_level(v);
   q[idx] = (uint8_t)lc;
   const float back = (lc / 255.0f) * 2.0f - 1.0f;  // Episode.load: .div(255).mul(2).sub(1)
   if (!(back == v)) *off_grid = 1;                 // benign race: every writer stores 1
@@ -1038,6 +1043,159 @@ extern "C" int dmd_segment_gather(const dmd_segment_gather_params* pp, dmd_strea
     hipLaunchKernelGGL(segment_gather_kernel<4>, grid, block, 0, (hipStream_t)stream, p, units);
   else
     hipLaunchKernelGGL(segment_gather_kernel<1>, grid, block, 0, (hipStream_t)stream, p, units);
+  DMD_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- open-loop world-model evaluation: one step closed on the device ------------------------------------------------------------
+// The sampler's frame `pred` against what the arena recorded at that episode step, then the ring advance from the prediction
+// (free running) or from the recording (teacher forced): the frame metrics in uint8 levels, the recorded reward / end of the
+// transition, two validity flags, the ring's oldest slot overwritten.  One workgroup per SAMPLE -- what its frame's target is (an
+// arena row, the final observation, or nothing) is uniform over the workgroup, the descriptor comes through scalar loads, and the
+// four metrics are reduced inside it: lanes' partial sums over the wave (__shfl_xor butterfly), the four waves through LDS, in a
+// fixed order; they are integers, so any order gives the same bits.  HBM-bound: per value 4 bytes of `pred` and 1 of the target
+// in, 4 bytes of ring (and 1 of levels) out.  Lanes walk the frame as dmd_segment_gather's do: 4-byte target words, 16-byte fp32
+// accesses, consecutive lanes on consecutive words (a wave's fp32 access is 1 KiB contiguous); W = 16 keeps four words 1 KiB apart
+// in flight per lane, W = 4 one; W = 1 is the any-size, any-alignment path.
+struct ol_sums {
+  unsigned long long sq, ab, off;
+  unsigned int mx;
+};
+
+// q = level(v) against the target level t; returns q
+__device__ __forceinline__ uint32_t ol_level(float v, uint32_t t, ol_sums& a) {
+  const int q = (int)dmd_level(v);
+  const int d = q - (int)t;
+  const unsigned int m = (unsigned int)(d < 0 ? -d : d);
+  a.sq += m * m;
+  a.ab += m;
+  a.off += m != 0 ? 1u : 0u;
+  a.mx = m > a.mx ? m : a.mx;
+  return (uint32_t)q;
+}
+
+__device__ __forceinline__ uint32_t ol_word(const f32x4 v, uint32_t tgt, ol_sums& a) {
+  uint32_t lv = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) lv |= ol_level(v[e], (tgt >> (8 * e)) & 0xff, a) << (8 * e);
+  return lv;
+}
+
+__device__ __forceinline__ unsigned long long ol_wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void openloop_step_kernel(dmd_openloop_params p) {
+  __shared__ unsigned long long red[4][4];
+  const int64_t b = blockIdx.x, pf = p.per_frame;
+  const int tid = threadIdx.x;
+  const int64_t first = p.seg[b * 4 + 0], start = p.seg[b * 4 + 1], len = p.seg[b * 4 + 2];
+  const int64_t final_row = p.finals ? p.seg[b * 4 + 3] : -1;
+  const int64_t s = start + p.T + p.step;  // the predicted frame's episode step; its transition is s - 1
+  const uint8_t* src = nullptr;            // nullptr: no recorded frame (invalid)
+  if (s >= 0 && s < len)
+    src = p.frames + (first + s) * pf;
+  else if (s == len && len >= 1 && final_row >= 0 && p.end[first + len - 1] != 0)
+    src = p.finals + final_row * pf;
+  const bool forced = p.teacher_forced != 0 && src != nullptr;
+  const float* pred = p.pred + b * pf;
+  float* ring = p.ctx_obs + (b * p.T + p.head) * pf;
+  uint8_t* lev = p.out_levels ? p.out_levels + b * pf : nullptr;
+  ol_sums a = {0ull, 0ull, 0ull, 0u};
+  if (W == 1) {
+    for (int64_t u = tid; u < pf; u += 256) {
+      const float v = pred[u];
+      const uint32_t t = src ? src[u] : 0u;
+      const uint32_t q = ol_level(v, t, a);
+      ring[u] = forced ? seg_dequant(t) : v;
+      if (lev) lev[u] = (uint8_t)q;
+    }
+  } else {
+    constexpr int U = W == 16 ? 4 : 1;  // words in flight per lane
+    const int64_t words = pf >> 2;
+    for (int64_t w0 = 0; w0 < words; w0 += 256 * U) {
+      f32x4 v[U];
+      uint32_t pk[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const int64_t w = w0 + k * 256 + tid;
+        pk[k] = 0u;
+        if (w < words) {
+          v[k] = *(const f32x4*)(pred + w * 4);
+          if (src) pk[k] = *(const uint32_t*)(src + w * 4);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const int64_t w = w0 + k * 256 + tid;
+        if (w < words) {
+          const uint32_t q = ol_word(v[k], pk[k], a);
+          *(f32x4*)(ring + w * 4) = forced ? seg_dequant4(pk[k]) : v[k];
+          if (lev) *(uint32_t*)(lev + w * 4) = q;
+        }
+      }
+    }
+  }
+  // every lane arrives here (no early exit above): wave butterflies, then the four waves in order
+  a.sq = ol_wave_sum(a.sq);
+  a.ab = ol_wave_sum(a.ab);
+  a.off = ol_wave_sum(a.off);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned int o = __shfl_xor(a.mx, off, 64);
+    a.mx = o > a.mx ? o : a.mx;
+  }
+  if ((tid & 63) == 0) {
+    red[tid >> 6][0] = a.sq;
+    red[tid >> 6][1] = a.ab;
+    red[tid >> 6][2] = a.mx;
+    red[tid >> 6][3] = a.off;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  unsigned long long m[4] = {0ull, 0ull, 0ull, 0ull};
+  if (src) {
+    for (int wv = 0; wv < 4; ++wv) {
+      m[0] += red[wv][0];
+      m[1] += red[wv][1];
+      m[2] = red[wv][2] > m[2] ? red[wv][2] : m[2];
+      m[3] += red[wv][3];
+    }
+  }
+  for (int k = 0; k < 4; ++k) p.metrics[b * 4 + k] = (int64_t)m[k];
+  const int64_t j = s - 1;
+  const bool tv = j >= 0 && j < len, sv = s >= 0 && s < len;
+  p.out_rew[b] = tv ? p.rew[first + j] : 0.0f;
+  p.out_end[b] = tv ? p.end[first + j] : (uint8_t)0;
+  p.out_valid[b * 2 + 0] = src ? 1 : 0;
+  p.out_valid[b * 2 + 1] = tv ? 1 : 0;
+  p.ctx_act[b * p.T + p.head] = sv ? p.act[first + s] : 0;
+}
+
+extern "C" int dmd_openloop_step(const dmd_openloop_params* pp, dmd_stream_t stream) {
+  DMD_CHECK_ARG(pp, "openloop_step: null parameter block");
+  const dmd_openloop_params& p = *pp;
+  DMD_CHECK_ARG(p.frames && p.act && p.rew && p.end && p.seg, "openloop_step: null arena array or descriptor");
+  DMD_CHECK_ARG(p.pred && p.ctx_obs && p.ctx_act, "openloop_step: null prediction or context ring");
+  DMD_CHECK_ARG(p.metrics && p.out_rew && p.out_end && p.out_valid, "openloop_step: null output (only out_levels is optional)");
+  DMD_CHECK_ARG(p.B >= 0 && p.T >= 1 && p.per_frame >= 1 && p.per_frame <= (1ll << 40), "openloop_step: B %d, T %d, per_frame %lld", p.B, p.T,
+                (long long)p.per_frame);
+  DMD_CHECK_ARG(p.step >= 0 && p.head >= 0 && p.head < p.T, "openloop_step: step %d (>= 0), head %d of a ring of %d", p.step, p.head, p.T);
+  DMD_CHECK_ARG(p.teacher_forced == 0 || p.teacher_forced == 1, "openloop_step: teacher_forced %d (0 or 1)", p.teacher_forced);
+  if (p.B == 0) return 0;
+  const uintptr_t u8_bases = (uintptr_t)p.frames | (uintptr_t)p.finals | (uintptr_t)p.out_levels;
+  const uintptr_t f32_bases = (uintptr_t)p.pred | (uintptr_t)p.ctx_obs;
+  const bool words = p.per_frame % 4 == 0 && u8_bases % 4 == 0 && f32_bases % 16 == 0;  // 4-byte level words, 16-byte fp32 accesses
+  const dim3 grid((unsigned)p.B), block(256);
+  if (words && p.per_frame % 16 == 0)
+    hipLaunchKernelGGL(openloop_step_kernel<16>, grid, block, 0, (hipStream_t)stream, p);
+  else if (words)
+    hipLaunchKernelGGL(openloop_step_kernel<4>, grid, block, 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(openloop_step_kernel<1>, grid, block, 0, (hipStream_t)stream, p);
   DMD_LAUNCH_CHECK();
   return 0;
 }

@@ -463,6 +463,48 @@ typedef struct dmd_segment_gather_params {
 } dmd_segment_gather_params;
 int dmd_segment_gather(const dmd_segment_gather_params* p, dmd_stream_t stream);
 
+/* ---- open-loop world-model evaluation against the replay arena: one step closed on the device in ONE launch ------------------
+ * (additive to ABI v11.)  The sampler has produced `pred` from the context rings; this call compares it with what the arena
+ * recorded and advances the rings, from the prediction (free running) or from the recording (teacher forced).
+ * Arena and descriptor: those of dmd_segment_gather.  For sample b the predicted frame is episode step s = start + T + step, it
+ * belongs to transition j = s - 1.
+ *   target   frames[first + s] when 0 <= s < len; finals[final_row] when s == len, final_row >= 0 and end[first + len - 1] != 0
+ *            (the put_back_final rule of dmd_segment_gather); otherwise the frame is INVALID
+ *   metrics  q = level(pred) = clamp(rint((v + 1) / 2 * 255), 0, 255) (dmd_quantize_u8's expression), d = q - target, in uint8 levels:
+ *            metrics[b] = { sum d^2, sum |d|, max |d|, count of d != 0 }; zeros for an invalid frame.  Exact integers.
+ *   truth    out_rew[b] = rew[first + j], out_end[b] = end[first + j] when 0 <= j < len, else zeros
+ *   flags    out_valid[b] = { frame valid, transition valid }
+ *   rings    ctx_obs[b][head] = pred[b]; with teacher_forced and a valid frame: the dequantised target, (u8 / 255) * 2 - 1 with the
+ *            bits of dmd_segment_gather.  ctx_act[b][head] = act[first + s] when 0 <= s < len, else 0.  `head` is the ring slot
+ *            the new frame goes to: the oldest one (the convention of dmd_edm_pack_input and dmd_reset_slots).
+ *   out_levels (optional, may be NULL) receives q.
+ * Nothing outside the episode is read (never an out-of-range address).  One workgroup per sample; the sums are reduced in a fixed
+ * order (and are integers).  Any per_frame >= 1: 16-byte accesses of pred / ctx_obs where per_frame % 4 == 0 and the pointers are
+ * aligned (pred / ctx_obs 16 bytes, frames / finals / out_levels 4; 16 levels per lane and pass where per_frame % 16 == 0, else 4);
+ * one level per lane otherwise. */
+typedef struct dmd_openloop_params {
+  int32_t B, T;
+  int64_t per_frame;       /* C * H * W */
+  int32_t step, head;      /* the evaluated step i >= 0; ring slot of the new frame, 0 <= head < T */
+  int32_t teacher_forced;  /* 0 or 1 */
+  int32_t reserved;
+  const uint8_t* frames;   /* (F, per_frame) */
+  const int64_t* act;      /* (F) */
+  const float* rew;        /* (F) */
+  const uint8_t* end;      /* (F) */
+  const uint8_t* finals;   /* (E, per_frame) or NULL */
+  const int64_t* seg;      /* (B, 4): first, start, len, final_row */
+  const float* pred;       /* (B, per_frame) */
+  float* ctx_obs;          /* (B, T, per_frame) ring */
+  int64_t* ctx_act;        /* (B, T) ring */
+  int64_t* metrics;        /* (B, 4) */
+  float* out_rew;          /* (B) */
+  uint8_t* out_end;        /* (B) */
+  uint8_t* out_valid;      /* (B, 2) */
+  uint8_t* out_levels;     /* (B, per_frame) or NULL */
+} dmd_openloop_params;
+int dmd_openloop_step(const dmd_openloop_params* p, dmd_stream_t stream);
+
 /* out[r] = row_slot[r] >= 0 ? slots[row_slot[r]] : base[r]  (rows of D floats): the burnt-in policy LSTM state of the reset rows
  * merged into the batch's state (env_loop.py:51-56), and the transposed operation for its backward:
  * d_base[r] = row_slot[r] >= 0 ? 0 : d_out[r] (d_base may be NULL);  d_slots[j] = slot_row[j] >= 0 ? d_out[slot_row[j]] : 0 */
