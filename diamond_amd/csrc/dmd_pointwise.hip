@@ -1199,3 +1199,181 @@ extern "C" int dmd_openloop_step(const dmd_openloop_params* pp, dmd_stream_t str
   DMD_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- per-frame SSIM of uint8 levels in fp64 (open-loop evaluation's structure metric) -------------------------------------------
+// Wang et al. 2004, 11 x 11 window of weights win[i] * win[j], positions whose window lies inside the frame; the contract and the
+// summation order are stated at dmd_frame_ssim in include/diamond_hip.h.  The window sum is SEPARABLE: a workgroup owns one
+// channel's tile of SSIM_S x SSIM_S positions, stages the (SSIM_S + 10)^2 levels of both operands in LDS (as floats: exact), forms
+// the five horizontal sums of its (SSIM_S + 10) x SSIM_S (row, column) pairs into LDS as doubles, and each lane then the five
+// vertical sums of its own position: 2 x 11 taps per moment where the direct form has 121.  fp64 throughout, no atomics: the
+// tile's two sums are reduced by a wave butterfly and then over the four waves in order, written to the workspace, and a second
+// launch adds a frame's tiles in one fixed order.  x and y go through the same operations (identical frames: exactly 1.0).
+// Compute-light (a 3 x 64 x 64 batch of 32: 1536 workgroups, ~75 kFLOP each); levels are read byte by byte, so any alignment.
+#define SSIM_S 16
+#define SSIM_IN (SSIM_S + DMD_SSIM_TAPS - 1)
+// level rows 48 floats apart: rows r and r + 1, which share a 32-lane group in the horizontal pass, sit on disjoint halves of the
+// 32 banks a 4-byte LDS read sees
+#define SSIM_LD 48
+
+__device__ __forceinline__ double ssim_wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// operand b of sample n in arena mode, nullptr where the sample has no target: the rule of openloop_step_kernel, restated (with
+// one shared device function that kernel's machine code changed, and its measurements and GPU runs are to stay valid) -- the
+// tests hold the two against each other on every kind of descriptor row
+__device__ __forceinline__ const uint8_t* ssim_arena_target(const dmd_ssim_params& p, int64_t n, int64_t pf) {
+  const int64_t first = p.seg[n * 4 + 0], start = p.seg[n * 4 + 1], len = p.seg[n * 4 + 2];
+  const int64_t final_row = p.finals ? p.seg[n * 4 + 3] : -1;
+  const int64_t s = start + p.T + p.step;
+  if (s >= 0 && s < len) return p.frames + (first + s) * pf;
+  if (s == len && len >= 1 && final_row >= 0 && p.end[first + len - 1] != 0) return p.finals + final_row * pf;
+  return nullptr;
+}
+
+__global__ __launch_bounds__(256) void frame_ssim_tile_kernel(dmd_ssim_params p, int tiles_x) {
+  __shared__ float lev[2][SSIM_IN][SSIM_LD];
+  __shared__ double hsum[5][SSIM_IN][SSIM_S];
+  __shared__ double red[4][2];
+  const int tid = threadIdx.x;
+  const int tile = blockIdx.x, c = blockIdx.y;
+  const int64_t n = blockIdx.z;
+  const int64_t plane = (int64_t)p.H * p.W, pf = plane * p.C;
+  const uint8_t* b_u8 = p.b_u8;
+  if (p.seg) {  // arena mode (uniform over the workgroup): a sample without a target is left to the second launch
+    b_u8 = ssim_arena_target(p, n, pf);
+    if (!b_u8) return;
+  } else if (b_u8) {
+    b_u8 += n * pf;
+  }
+  const int64_t base = n * pf + c * plane;
+  const int y0 = (tile / tiles_x) * SSIM_S, x0 = (tile % tiles_x) * SSIM_S;
+  // 1. the levels of the tile and its 10-wide apron; outside the frame: zeros (they reach only positions that do not count)
+  for (int i = tid; i < SSIM_IN * SSIM_IN; i += 256) {
+    const int r = i / SSIM_IN, q = i - r * SSIM_IN;
+    const int y = y0 + r, x = x0 + q;
+    float va = 0.0f, vb = 0.0f;
+    if (y < p.H && x < p.W) {
+      const int64_t at = (int64_t)y * p.W + x;
+      va = p.a_u8 ? (float)p.a_u8[base + at] : dmd_level(p.a_f32[base + at]);
+      vb = b_u8 ? (float)b_u8[c * plane + at] : dmd_level(p.b_f32[base + at]);
+    }
+    lev[0][r][q] = va;
+    lev[1][r][q] = vb;
+  }
+  __syncthreads();
+  // 2. horizontal sums, taps ascending
+  for (int i = tid; i < SSIM_IN * SSIM_S; i += 256) {
+    const int r = i / SSIM_S, q = i - r * SSIM_S;
+    double sx = 0.0, sy = 0.0, sxx = 0.0, syy = 0.0, sxy = 0.0;
+#pragma unroll
+    for (int k = 0; k < DMD_SSIM_TAPS; ++k) {
+      const double w = p.win[k], x = (double)lev[0][r][q + k], y = (double)lev[1][r][q + k];
+      sx += w * x;
+      sy += w * y;
+      sxx += w * (x * x);
+      syy += w * (y * y);
+      sxy += w * (x * y);
+    }
+    hsum[0][r][q] = sx;
+    hsum[1][r][q] = sy;
+    hsum[2][r][q] = sxx;
+    hsum[3][r][q] = syy;
+    hsum[4][r][q] = sxy;
+  }
+  __syncthreads();
+  // 3. vertical sums of this lane's position, taps ascending; then the two ratios
+  const int ty = tid / SSIM_S, tx = tid - ty * SSIM_S;
+  double m[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int k = 0; k < DMD_SSIM_TAPS; ++k) {
+    const double w = p.win[k];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) m[j] += w * hsum[j][ty + k][tx];
+  }
+  double ssim = 0.0, cs = 0.0;
+  if (y0 + ty < p.H - (DMD_SSIM_TAPS - 1) && x0 + tx < p.W - (DMD_SSIM_TAPS - 1)) {
+    const double mx = m[0], my = m[1];
+    const double vxx = m[2] - mx * mx, vyy = m[3] - my * my, vxy = m[4] - mx * my;
+    cs = (2.0 * vxy + p.c2) / (vxx + vyy + p.c2);
+    ssim = (2.0 * (mx * my) + p.c1) / (mx * mx + my * my + p.c1) * cs;
+  }
+  // 4. the tile's sums: every lane arrives here; wave butterflies, then the four waves in order
+  ssim = ssim_wave_sum(ssim);
+  cs = ssim_wave_sum(cs);
+  if ((tid & 63) == 0) {
+    red[tid >> 6][0] = ssim;
+    red[tid >> 6][1] = cs;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  double t0 = 0.0, t1 = 0.0;
+  for (int wv = 0; wv < 4; ++wv) {
+    t0 += red[wv][0];
+    t1 += red[wv][1];
+  }
+  double* part = p.workspace + ((n * p.C + c) * (int64_t)gridDim.x + tile) * 2;
+  part[0] = t0;
+  part[1] = t1;
+}
+
+// one wave per frame: lane l adds the frame's partials l, l + 64, ... in ascending order, then the butterfly
+__global__ __launch_bounds__(64) void frame_ssim_mean_kernel(dmd_ssim_params p, int64_t parts) {
+  const int64_t n = blockIdx.x;
+  const int lane = threadIdx.x;
+  const bool valid = !p.seg || ssim_arena_target(p, n, (int64_t)p.H * p.W * p.C) != nullptr;  // uniform over the wave
+  double s0 = 0.0, s1 = 0.0;
+  if (valid) {
+    const double* part = p.workspace + n * parts * 2;
+    for (int64_t i = lane; i < parts; i += 64) {
+      s0 += part[i * 2 + 0];
+      s1 += part[i * 2 + 1];
+    }
+  }
+  s0 = ssim_wave_sum(s0);
+  s1 = ssim_wave_sum(s1);
+  if (lane != 0) return;
+  const double count = (double)((int64_t)p.C * (p.H - (DMD_SSIM_TAPS - 1)) * (p.W - (DMD_SSIM_TAPS - 1)));
+  const double none = __builtin_nan("");  // a sample without a target
+  p.out[n * 2 + 0] = valid ? s0 / count : none;
+  p.out[n * 2 + 1] = valid ? s1 / count : none;
+}
+
+static bool ssim_sizes_ok(int64_t N, int64_t C, int64_t H, int64_t W) {
+  return N >= 0 && N <= 65535 && C >= 1 && C <= 65535 && H >= DMD_SSIM_TAPS && W >= DMD_SSIM_TAPS && H <= 32768 && W <= 32768;
+}
+
+static int64_t ssim_tiles(int64_t extent) { return (extent - (DMD_SSIM_TAPS - 1) + SSIM_S - 1) / SSIM_S; }
+
+extern "C" int64_t dmd_ssim_workspace_doubles(int N, int C, int H, int W) {
+  if (!ssim_sizes_ok(N, C, H, W)) return 0;
+  return 2 * (int64_t)N * C * ssim_tiles(H) * ssim_tiles(W);
+}
+
+extern "C" int dmd_frame_ssim(const dmd_ssim_params* pp, dmd_stream_t stream) {
+  DMD_CHECK_ARG(pp, "frame_ssim: null parameter block");
+  const dmd_ssim_params& p = *pp;
+  DMD_CHECK_ARG(p.H >= DMD_SSIM_TAPS && p.W >= DMD_SSIM_TAPS, "frame_ssim: frames of %d x %d, the window needs %d x %d", p.H, p.W, DMD_SSIM_TAPS,
+                DMD_SSIM_TAPS);
+  DMD_CHECK_ARG(ssim_sizes_ok(p.N, p.C, p.H, p.W), "frame_ssim: N %d (0 ... 65535), C %d (1 ... 65535), H %d, W %d (11 ... 32768)", p.N, p.C, p.H, p.W);
+  DMD_CHECK_ARG((p.a_f32 != nullptr) != (p.a_u8 != nullptr), "frame_ssim: operand a needs exactly one of a_f32 / a_u8");
+  const bool arena = p.frames || p.finals || p.end || p.seg;
+  if (arena) {
+    DMD_CHECK_ARG(!p.b_f32 && !p.b_u8, "frame_ssim: a direct operand b together with arena fields");
+    DMD_CHECK_ARG(p.frames && p.end && p.seg, "frame_ssim: arena mode needs frames, end and seg");
+  } else {
+    DMD_CHECK_ARG((p.b_f32 != nullptr) != (p.b_u8 != nullptr), "frame_ssim: operand b needs exactly one of b_f32 / b_u8 (or the arena fields)");
+  }
+  DMD_CHECK_ARG(p.T >= 0 && p.step >= 0, "frame_ssim: T %d, step %d (both >= 0)", p.T, p.step);
+  DMD_CHECK_ARG(p.out && p.workspace, "frame_ssim: null out or workspace");
+  if (p.N == 0) return 0;
+  const int64_t tx = ssim_tiles(p.W), ty = ssim_tiles(p.H);
+  DMD_CHECK_ARG(tx * ty * p.C * p.N <= 0x7fffffffLL, "frame_ssim: %lld workgroups: beyond one launch's grid", (long long)(tx * ty * p.C * p.N));
+  hipLaunchKernelGGL(frame_ssim_tile_kernel, dim3((unsigned)(tx * ty), (unsigned)p.C, (unsigned)p.N), dim3(256), 0, (hipStream_t)stream, p, (int)tx);
+  DMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(frame_ssim_mean_kernel, dim3((unsigned)p.N), dim3(64), 0, (hipStream_t)stream, p, tx * ty * p.C);
+  DMD_LAUNCH_CHECK();
+  return 0;
+}

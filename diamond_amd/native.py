@@ -123,6 +123,16 @@ class OpenLoopParams(C.Structure):
                 ("out_valid", C.c_void_p), ("out_levels", C.c_void_p)]
 
 
+SSIM_TAPS = 11
+
+
+class SsimParams(C.Structure):
+    _fields_ = [("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("a_f32", C.c_void_p), ("a_u8", C.c_void_p),
+                ("b_f32", C.c_void_p), ("b_u8", C.c_void_p), ("frames", C.c_void_p), ("finals", C.c_void_p), ("end", C.c_void_p),
+                ("seg", C.c_void_p), ("T", C.c_int32), ("step", C.c_int32), ("win", C.c_double * SSIM_TAPS), ("c1", C.c_double),
+                ("c2", C.c_double), ("workspace", C.c_void_p), ("out", C.c_void_p)]
+
+
 CHAIN_MAX_BLOCKS = 8
 
 
@@ -146,7 +156,7 @@ EXPORTS = (
     "dmd_pack_conv_weight_f16x2", "dmd_linear", "dmd_attention", "dmd_attention_valid", "dmd_attention_f32", "dmd_attention_f16x2", "dmd_attention_bwd", "dmd_attention_bwd_valid",
     "dmd_attention_bwd_mfma", "dmd_attention_bwd_workspace_floats",
     "dmd_edm_pack_input", "dmd_cond_embed", "dmd_edm_denoised", "dmd_euler_step", "dmd_heun_step", "dmd_quantize_u8", "dmd_reset_state",
-    "dmd_dequant_gather", "dmd_segment_gather", "dmd_openloop_step", "dmd_resolve_deaths", "dmd_reset_slots", "dmd_merge_slots", "dmd_merge_slots_bwd", "dmd_nchw_to_nhwc",
+    "dmd_dequant_gather", "dmd_segment_gather", "dmd_openloop_step", "dmd_frame_ssim", "dmd_ssim_workspace_doubles", "dmd_resolve_deaths", "dmd_reset_slots", "dmd_merge_slots", "dmd_merge_slots_bwd", "dmd_nchw_to_nhwc",
     "dmd_nhwc_to_nchw", "dmd_gn_stats", "dmd_gn_stats_valid", "dmd_maxpool2", "dmd_lstm_pointwise", "dmd_lstm_pointwise_bwd", "dmd_lambda_returns", "dmd_categorical_sample", "dmd_rew_end_loss",
     "dmd_maxpool2_bwd", "dmd_gn_bwd_workspace_bytes", "dmd_gn_silu_bwd", "dmd_wgrad_workspace_floats", "dmd_conv2d_wgrad", "dmd_wgrad_job", "dmd_wgrad_reduce_jobs",
     "dmd_conv2d_dgrad_input", "dmd_lowres_chain", "dmd_lowres_chain32", "dmd_last_error", "dmd_abi_version", "dmd_reload_env",
@@ -155,7 +165,7 @@ EXPORTS = (
 # entry points that launch kernels (everything except queries / packing helpers that bench.py does not time)
 LAUNCHERS = frozenset(n for n in EXPORTS if n not in (
     "dmd_conv2d_kernel_name", "dmd_conv_stat_tiles", "dmd_conv2d_f16x2_eligible", "dmd_conv1x1_stream_eligible",
-    "dmd_conv2d_proj_eligible", "dmd_attention_bwd_workspace_floats", "dmd_gn_bwd_workspace_bytes", "dmd_wgrad_workspace_floats", "dmd_wgrad_job", "dmd_last_error",
+    "dmd_conv2d_proj_eligible", "dmd_attention_bwd_workspace_floats", "dmd_gn_bwd_workspace_bytes", "dmd_wgrad_workspace_floats", "dmd_wgrad_job", "dmd_ssim_workspace_doubles", "dmd_last_error",
     "dmd_abi_version", "dmd_reload_env"))
 
 
@@ -255,6 +265,9 @@ def declare_signatures(L: C.CDLL) -> None:
                                      C.c_int, C.c_void_p]
     L.dmd_segment_gather.argtypes = [C.POINTER(SegmentGatherParams), C.c_void_p]
     L.dmd_openloop_step.argtypes = [C.POINTER(OpenLoopParams), C.c_void_p]
+    L.dmd_frame_ssim.argtypes = [C.POINTER(SsimParams), C.c_void_p]
+    L.dmd_ssim_workspace_doubles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    L.dmd_ssim_workspace_doubles.restype = C.c_int64
     L.dmd_reset_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.dmd_resolve_deaths.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

@@ -505,6 +505,56 @@ typedef struct dmd_openloop_params {
 } dmd_openloop_params;
 int dmd_openloop_step(const dmd_openloop_params* p, dmd_stream_t stream);
 
+/* ---- per-frame SSIM of uint8 levels, in fp64, on the device ---------------------------------------------------------------------
+ * (additive to ABI v11.)  Wang et al. 2004 as the common implementations compute it: operands are levels 0 ... 255 as fp64, a
+ * window of 11 taps per axis with weight win[i] * win[j] at tap (i, j), and only the positions whose window lies wholly inside the
+ * frame: (H - 10) * (W - 10) per channel.  Per position and channel, with x from `a` and y from `b`:
+ *   mx = sum w x, my = sum w y, sxx = sum w x^2 - mx^2, syy = sum w y^2 - my^2, sxy = sum w x y - mx my
+ *   cs = (2 sxy + c2) / (sxx + syy + c2)          ssim = (2 mx my + c1) / (mx^2 + my^2 + c1) * cs
+ *   out[n] = { mean ssim, mean cs } over the C * (H - 10) * (W - 10) positions of frame n.
+ * win, c1 and c2 come from the host (the kernel holds no exp): diamond_amd/metrics.py forms the normalised Gaussian and
+ * c1 = (0.01 * 255)^2, c2 = (0.03 * 255)^2.
+ * Operand a: N frames (N, C, H, W) contiguous, through EXACTLY ONE of a_f32 (values in [-1, 1]; the level is
+ *   clamp(rint((v + 1) / 2 * 255), 0, 255), the expression dmd_openloop_step compares with and dmd_quantize_u8 stores) and a_u8 (levels).
+ * Operand b, one of two modes:
+ *   direct  exactly one of b_f32 / b_u8, N contiguous frames; every arena field NULL
+ *   arena   b_f32 = b_u8 = NULL; frames, end, seg (and finals, which may be NULL) are those of dmd_openloop_step, and the target of
+ *           sample n is resolved by ITS rule: arena row first + s with
+ *           s = start + T + step when 0 <= s < len; finals[final_row] when s == len, final_row >= 0 and end[first + len - 1] != 0;
+ *           otherwise the sample has no target and out[n] = { NaN, NaN }.  Nothing outside the episode is read.
+ * Arithmetic: fp64 throughout, no atomics, ONE summation order, so a shape's result is bitwise the same from run to run:
+ *   the window sum is SEPARABLE -- a workgroup takes one channel's tile of 16 x 16 positions, stages the 26 x 26 levels of both
+ *   operands in LDS, forms the five horizontal sums (x, y, x^2, y^2, x y; taps 0 ... 10 ascending, from 0.0) for its 26 x 16 (row,
+ *   position column) pairs into LDS, then each lane the five vertical sums of its position (taps ascending, from 0.0);
+ *   the tile's ssim / cs sums: a __shfl_xor butterfly over each wave (offsets 32, 16, ... 1), then waves 0 ... 3 in order; positions
+ *   beyond the frame's last contribute +0.0.  The pair goes to workspace[((n * C + c) * tiles + tile)] (tile = ty * tiles_x + tx).
+ *   A second launch of the same call: one wave per frame, lane l adds the frame's partials l, l + 64, ... in ascending order, the
+ *   same butterfly follows, and lane 0 divides by the count.  x and y go through identical operations: identical frames give
+ *   exactly { 1.0, 1.0 }.
+ * workspace: dmd_ssim_workspace_doubles(N, C, H, W) doubles (2 * N * C * ceil((H - 10) / 16) * ceil((W - 10) / 16); 0 for sizes
+ * the entry refuses), overwritten by every call.  Any C >= 1, any H, W >= 11, any alignment (levels are read byte by byte).
+ * Refused (non-zero, dmd_last_error): H or W below 11; both or neither pointer of an operand; a direct b together with an arena
+ * field; an arena without frames / end / seg; T < 0 or step < 0; NULL out or workspace.  N == 0 returns 0 and launches nothing. */
+#define DMD_SSIM_TAPS 11
+typedef struct dmd_ssim_params {
+  int32_t N, C, H, W;
+  const float* a_f32;      /* (N, C, H, W) in [-1, 1], or NULL */
+  const uint8_t* a_u8;     /* (N, C, H, W) levels, or NULL */
+  const float* b_f32;      /* direct mode: as a */
+  const uint8_t* b_u8;
+  const uint8_t* frames;   /* arena mode: (F, C * H * W) */
+  const uint8_t* finals;   /* (E, C * H * W) or NULL */
+  const uint8_t* end;      /* (F) */
+  const int64_t* seg;      /* (N, 4): first, start, len, final_row */
+  int32_t T, step;         /* arena mode: context length, evaluated step >= 0 */
+  double win[DMD_SSIM_TAPS];
+  double c1, c2;
+  double* workspace;       /* dmd_ssim_workspace_doubles(N, C, H, W) doubles */
+  double* out;             /* (N, 2): mean ssim, mean cs */
+} dmd_ssim_params;
+int64_t dmd_ssim_workspace_doubles(int N, int C, int H, int W);
+int dmd_frame_ssim(const dmd_ssim_params* p, dmd_stream_t stream);
+
 /* out[r] = row_slot[r] >= 0 ? slots[row_slot[r]] : base[r]  (rows of D floats): the burnt-in policy LSTM state of the reset rows
  * merged into the batch's state (env_loop.py:51-56), and the transposed operation for its backward:
  * d_base[r] = row_slot[r] >= 0 ? 0 : d_out[r] (d_base may be NULL);  d_slots[j] = slot_row[j] >= 0 ? d_out[slot_row[j]] : 0 */

@@ -13,6 +13,11 @@ native.PROFILER's hook, every device kernel (torch's included) from a torch.prof
 Prints one JSON line and writes it to profiles/openloop_eval.json.  Needs the GPU (there is no CPU path to time):
 
     timeout -k 10 900 python tools/openloop_bench.py
+
+`--ssim`: what `open_loop_eval(..., ssim=True)` costs instead -- arm `ssim_off` (exactly the launches above) against arm `ssim_on`
+(one dmd_frame_ssim call per step more) in the same alternating blocks, the entry point's own time from a replayed graph of
+`--ssim-graph-calls` arena-mode calls, and its largest difference from the 121-tap numpy restatement (tests/ssim_cases.py) over
+the GPU tests' production shapes.  Writes profiles/openloop_ssim.json.
 """
 import argparse
 import json
@@ -60,6 +65,100 @@ def device_kernels(fn):
         return None
 
 
+def blocks_ms(arms, blocks, evals):
+    """ms per evaluation of every arm over alternating blocks (HIP events around a block, which ends in a synchronise)."""
+    ms = {name: [] for name in arms}
+    for _ in range(blocks):
+        for name, fn in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(evals):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1) / evals)
+    return ms
+
+
+def ssim_arms(args, sampler, agent, store, ids, t):
+    import ctypes
+
+    from diamond_amd import native as nv
+    from diamond_amd.metrics import frame_ssim, set_operand, ssim_params, ssim_workspace
+    from diamond_amd.openloop import open_loop_eval
+    from tests import ssim_cases as SC
+
+    dev, b, horizon, tf = store.device, args.batch, args.horizon, args.teacher_forced
+    arms = {"ssim_off": lambda: open_loop_eval(sampler, agent.rew_end_model, store, ids, horizon, teacher_forced=tf),
+            "ssim_on": lambda: open_loop_eval(sampler, agent.rew_end_model, store, ids, horizon, teacher_forced=tf, ssim=True)}
+    noise = torch.randn(horizon, b, *FRAME, device=dev)
+    reports = {}
+    for name, fn in arms.items():  # the same injected draws: ssim changes no other field
+        left = list(noise)
+        sampler.noise_fn = lambda shape, d: left.pop()
+        reports[name] = fn()
+    sampler.noise_fn = None
+    same = all(torch.equal(getattr(reports["ssim_on"], k), getattr(reports["ssim_off"], k)) for k in
+               ("sq_err", "abs_err", "max_err", "pixels_off", "frame_valid", "transition_valid", "logits_rew", "logits_end", "ctx_obs"))
+    sm = reports["ssim_on"].summary()
+    for fn in arms.values():
+        fn()
+    torch.cuda.synchronize()
+    ms = blocks_ms(arms, args.blocks, args.evals)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    spread = {k: max(v) - min(v) for k, v in ms.items()}
+
+    # the entry point alone: a graph of arena-mode calls on a prediction-shaped operand, replayed
+    seg = torch.from_numpy(store._descriptor(ids)[0]).to(dev)
+    pred = torch.rand((b,) + FRAME, device=dev) * 2 - 1
+    p = ssim_params(b, *FRAME)
+    set_operand(p, "a", pred)
+    work, out = ssim_workspace(p, dev), torch.empty((b, 2), dtype=torch.float64, device=dev)
+    p.frames, p.finals, p.end, p.seg = (nv.ptr(x) for x in (store.frames, store.finals, store.end, seg))
+    p.T, p.step, p.workspace, p.out = t, 0, nv.ptr(work), nv.ptr(out)
+    call = lambda: nv.check(nv.lib().dmd_frame_ssim(ctypes.byref(p), nv.stream()), "dmd_frame_ssim")
+    call()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(args.ssim_graph_calls):
+            call()
+    graph.replay()
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(args.blocks):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        graph.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        us.append(e0.elapsed_time(e1) * 1000.0 / args.ssim_graph_calls)
+
+    worst = {}
+    for shape in ((11, 3, 64, 64), (2, 3, 256, 256), (2, 3, 68, 76)):
+        x, y = SC.pair("plus minus 2", shape, seed=1)
+        got = frame_ssim(torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)).cpu().numpy()
+        worst["x".join(map(str, shape))] = float(np.abs(got - SC.restate(x, y)).max())
+
+    diff = med["ssim_on"] - med["ssim_off"]
+    line = {"what": "open_loop_eval(ssim=True) against ssim=False of the same tree, ms per evaluation (HIP events around alternating blocks)",
+            "device": torch.cuda.get_device_name(0), "batch": b, "horizon": horizon, "context": t, "frame": list(FRAME),
+            "denoising_steps": args.denoising_steps, "teacher_forced": tf, "evals_per_block": args.evals, "blocks_per_arm": args.blocks,
+            "other_fields_agree_bitwise": bool(same), "median_ms": {k: round(v, 4) for k, v in med.items()},
+            "spread_ms": {k: round(v, 4) for k, v in spread.items()}, "blocks_ms": {k: [round(x, 4) for x in v] for k, v in ms.items()},
+            "ssim_on_minus_off_ms": round(diff, 4), "increase_exceeds_larger_spread": bool(diff > max(spread.values())),
+            "frame_ssim_call_us_graph_replay": {"calls_per_graph": args.ssim_graph_calls, "median": round(statistics.median(us), 3),
+                                                "blocks": [round(x, 3) for x in us]},
+            "frame_ssim_calls_per_evaluation": horizon, "summary_ssim": sm["ssim"], "summary_ssim_cs": sm["ssim_cs"],
+            "max_abs_diff_from_restatement": {"tolerance": SC.TOL, "device": worst, "interpreter": args.interpreter_max_diff}}
+    text = json.dumps(line)
+    print(text, flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch", type=int, default=32)
@@ -71,8 +170,14 @@ def main():
     ap.add_argument("--blocks", type=int, default=5, help="blocks per arm")
     ap.add_argument("--teacher-forced", action="store_true")
     ap.add_argument("--no-kernel-trace", action="store_true", help="count the C-ABI launches only (no torch.profiler pass)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "openloop_eval.json"))
+    ap.add_argument("--ssim", action="store_true", help="time open_loop_eval(ssim=True) against ssim=False instead")
+    ap.add_argument("--ssim-graph-calls", type=int, default=200, help="dmd_frame_ssim calls in the replayed graph")
+    ap.add_argument("--interpreter-max-diff", type=float, default=None,
+                    help="recorded as given: the largest difference tests/test_ssim_simt.py printed (pytest -s)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "openloop_ssim.json" if args.ssim else "openloop_eval.json")
     if not torch.cuda.is_available():
         sys.exit("openloop_bench: no GPU visible -- NOT measured (a time exists on the device only)")
 
@@ -112,6 +217,9 @@ def main():
         ids_h = [(e, s, s + t + h) for e, s in starts]
         return {"open_loop_eval": lambda: open_loop_eval(sampler, agent.rew_end_model, store, ids_h, h, teacher_forced=tf),
                 "reference_loop": lambda: reference_loop(sampler, agent.rew_end_model, store, ids_h, t, h, tf)}
+
+    if args.ssim:
+        return ssim_arms(args, sampler, agent, store, ids, t)
 
     arms = make_arms(horizon)
 
