@@ -13,6 +13,16 @@
 // LOUDLY instead of silently saturating, and NaN / Inf inputs stay non-finite exactly where F.conv2d's would
 // (tests/test_gpu_precision.py).  Operands below 2^-25 in magnitude are flushed (absolute floor): tensors whose scale
 // is far below 1 (gradients) are pre-scaled by a power of two by the caller (ac_native._EncoderFn.backward).
+// GroupNorm contract (include/diamond_hip.h states it for callers; tests/test_groupnorm_precision.py pins both parts):
+//   * the producers normalise as fma(x, a, b) with b = add - mean * a rounded to fp32: every normalised value of a channel
+//     carries half an ulp of b, up to 2^-24 (|mean| rstd |mul'| + |add|).  fp32-class up to |mean| rstd = 32; a group constant
+//     at v != 0 has |mean| rstd = 316 |v| (measured at v = -3.25: 0.8 .. 1.6e-5 of the output scale, at most 1.37 of the
+//     root-sum-square of that term through the weights).  (x - mean) * a + add is exact there; it needs the mean as a fourth
+//     table row and four more registers per staging thread.  The extra VALU instruction alone measured 13,357 against 13,375
+//     frames/s (three alternating benchmark runs each, +-0.3 % spread): profiles/groupnorm_precision.txt.
+//   * out_stats: fp32 sums of a lane's 16 outputs (16x16 geometries), 32 .. 64 (8x8, fused projection: StatAcc = float, at
+//     the register cap), float64 from there: rstd off by up to 2^-24 (1 + r^2), r = |mean| / sigma of the output group
+//     (measured 0.27 of that); the next prologue's fp32-class bound holds to r = 30 (16x16, projection) / r = 15 (8x8).
 //
 // Structure.  One 768-thread workgroup per CU is split by ROLE:
 //   * waves 0-3 and 4-7 = two CONSUMER groups that take alternate tiles: the group whose tile is

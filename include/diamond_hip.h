@@ -106,7 +106,21 @@ typedef struct dmd_conv_params {
  *   be inside the fp16 range (|x| < 65520); nothing is clamped, an operand beyond it makes every output it
  *   touches NaN (loud, never a silently wrong finite value), NaN / Inf inputs stay non-finite.  Honoured only
  *   where dmd_conv2d_f16x2_eligible() says so (3x3 / 1x1 stride 1, Cout in {32, 64}, Cin <= 128 / 64, NHWC
- *   out, or the few-channel NCHW head); everything else uses the exact kernel. */
+ *   out, or the few-channel NCHW head); everything else uses the exact kernel.
+ *   GROUPNORM CONTRACT of that kernel (conv_f16ws_kernel; tests/test_groupnorm_precision.py walks its edges, measured table in
+ *   profiles/groupnorm_precision.txt).  Everywhere else GroupNorm is (x - mean) * a + add on float64 sums.
+ *   (1) Prologue: a normalised source is evaluated as fma(x, a, b), b = add - mean * a rounded to fp32, so every normalised
+ *       value of a channel carries half an ulp of b: up to delta = 2^-24 (|mean| rstd |mul'| + |add|).  Up to |mean| rstd = 32
+ *       (mean = 30 sigma included) that stays inside fp32-class accuracy of the output; a group CONSTANT at v != 0 (variance
+ *       0, rstd = 316) is |mean| rstd = 316 |v|: its output is `add` only to 1.9e-5 |v mul'| (the (x - mean) * a paths give
+ *       `add` exactly).  Measured on the MI355X at v = -3.25: 0.8 .. 1.6e-5 of the convolution's output scale, 0.2 .. 1.37 of
+ *       the root-sum-square of delta through the weights; the tests allow 2 x that root-sum-square beyond the edge.
+ *   (2) Epilogue: out_stats are float64 sums of fp32 partial sums -- of a lane's 16 outputs in the 16x16 geometries, of its
+ *       32 .. 64 in the 8x8 and fused-projection ones (at the register cap) -- so the consumer's rstd is that of a mean square
+ *       rounded once to fp32: off by up to 2^-24 (1 + r^2), r = |mean| / sigma of the output group (measured 0.27 of that:
+ *       1.7e-5 at r = 30, 4e-6 at r = 15).  The next prologue holds its fp32-class bound up to r = 30 on the 16x16 and
+ *       fused-projection geometries and up to r = 15 on the 8x8 ones; an output with a larger offset that needs float64
+ *       statistics takes dmd_gn_stats of it instead. */
 #define DMD_PRECISION_F32 0
 #define DMD_PRECISION_F16X2 1
 int dmd_conv2d_f16x2_eligible(const dmd_conv_params* p);
