@@ -635,9 +635,16 @@ __device__ __forceinline__ void wg_unpack8(const float (&r)[8], wg_h8& h, wg_h8&
 //   false  exact: v_mfma_f32_16x16x4_f32, an fp32 fma chain over the pixels, each tile strictly load -> LDS -> barrier -> MFMA
 //   true   the staged activations and dy are kept as packed split-fp16 pairs (same 4 bytes per value, same LDS layout, the same
 //          two-lanes-per-bank ds_read_b32 pattern: lane (i, kg) supplies pixels (row r, column kg + 4 h), r < 4, h < 2) and 32
-//          pixels are contracted per v_mfma_f32_16x16x32_f16 x 3 -- 12 instead of 128 matrix-pipe cycles per 16 pixels -- with
+//          pixels are contracted per v_mfma_f32_16x16x32_f16 x 4 -- 16 instead of 128 matrix-pipe cycles per 16 pixels -- with
 //          the NEXT tile's global loads issued before the MFMA phase of the current one and held in registers (one workgroup
 //          per CU, 512 registers per lane: ~84 of them carry the tile in flight).  The bias gradient sums the raw dy.
+//          OPERAND CONTRACT (include/diamond_hip.h at dmd_wgrad_params.precision has the full text and the measured table;
+//          tests/test_wgrad_precision.py pins it): |x| < 65520, |x - (h + l)| <= max(2^-22 |x|, 2^-25); all four products are
+//          summed, l l + h l + l h + h h, smallest first (l l is up to 2^-22 of a product; its MFMA takes no register).  A finite
+//          |x| >= 65520 gives h = inf, l = -inf: a dy entry turns its whole row dw[co] into NaN, a source entry its whole column
+//          dw[.][ci] -- never a finite wrong number; db stays the finite raw sum.  The floor bites PER ROW: one scalar scales
+//          the launch to O(1), and a row whose dy is below 2^-3 of that has subnormal l pieces (absolute error 2^-25); its
+//          relative error grows as the inverse of its scale.
 // Round 4, measured (profiles/r04_staged_wgrad_ab.txt, r04_ab_train.txt; denoiser training step at batch 32, one hipGraph):
 // 16-pixel MFMAs without prefetch on up to 1024 workgroups 13.99 ms -> 32-pixel MFMAs 13.53 -> + prefetch 13.11 -> at most 256
 // workgroups (each writes one 147 KB partial of the whole gradient: a quarter of the reduction traffic) 12.01; a one-pass
@@ -669,6 +676,7 @@ __device__ __forceinline__ void wgrad_mfma_k32(f32x4 (&acc)[G::NCO][G::CB], cons
       wg_unpack8(r, bh, bl);
 #pragma unroll
       for (int a = 0; a < G::NCO; ++a) {
+        acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[a], bl, acc[a][b], 0, 0, 0);
         acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[a], bl, acc[a][b], 0, 0, 0);
         acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[a], bh, acc[a][b], 0, 0, 0);
         acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[a], bh, acc[a][b], 0, 0, 0);
@@ -677,6 +685,7 @@ __device__ __forceinline__ void wgrad_mfma_k32(f32x4 (&acc)[G::NCO][G::CB], cons
   }
 }
 
+#define WGRAD_CHAIN_TILES 16  // exact route: tiles (of 128 pixels) per accumulator chain
 template <class G, bool SPLIT>
 __global__ __launch_bounds__(256) void wgrad_kernel(const dmd_wgrad_params p, int tiles_total, int tiles_per_wg) {
   DMD_DYNAMIC_LDS(float, smem);
@@ -711,6 +720,9 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const dmd_wgrad_params p, in
   const int tile_begin = blockIdx.x * tiles_per_wg;
   const int tile_end = min(tiles_total, tile_begin + tiles_per_wg);
   int tab_n0 = -1, tab_n1 = -1;
+  constexpr int PER_TOTAL = G::NB * G::NCO * 256 + G::COUT;  // [weights partial | bias partial] per workgroup
+  float* part = p.workspace + (size_t)blockIdx.x * PER_TOTAL;
+  bool flushed = false;  // (exact route only) the partial already holds the first WGRAD_CHAIN_TILES * k tiles
 
   if constexpr (SPLIT) {
     // ---- software-pipelined tile loop: raw loads of tile t + 1 fly under the MFMA phase of tile t ----
@@ -876,17 +888,37 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const dmd_wgrad_params p, in
 #pragma unroll
         for (int a = 0; a < G::NCO; ++a) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a], bv[b], acc[a][b], 0, 0, 0);
     }
+    // A chain of one fp32 rounding per 4 pixels collects them like a random walk, sqrt(n) of them on a coherent sum: every
+    // WGRAD_CHAIN_TILES tiles the accumulators move into the workgroup's own partial (a lane adds to the slots it alone writes)
+    // and restart at zero.  Plans of up to WGRAD_CHAIN_TILES tiles per workgroup -- the denoiser's at the training batch --
+    // never get here and keep their bits.
+    if ((tile - tile_begin + 1) % WGRAD_CHAIN_TILES == 0 && tile + 1 < tile_end) {
+#pragma unroll
+      for (int s = 0; s < G::CB; ++s) {
+        const int b = wave + 4 * s;
+        if (b < G::NB) {
+#pragma unroll
+          for (int a = 0; a < G::NCO; ++a) {
+            f32x4* slot = (f32x4*)(part + ((size_t)(b * G::NCO + a) * 64 + lane) * 4);
+            *slot = flushed ? *slot + acc[a][s] : acc[a][s];
+            acc[a][s] = (f32x4){0.f, 0.f, 0.f, 0.f};
+          }
+        }
+      }
+      flushed = true;
+    }
   }
 
   // ---- partial results: [wg][NB][NCO][64 lanes][4] ----
-  constexpr int PER_TOTAL = G::NB * G::NCO * 256 + G::COUT;  // [weights partial | bias partial] per workgroup
-  float* part = p.workspace + (size_t)blockIdx.x * PER_TOTAL;
 #pragma unroll
   for (int s = 0; s < G::CB; ++s) {
     const int b = wave + 4 * s;
     if (b < G::NB) {
 #pragma unroll
-      for (int a = 0; a < G::NCO; ++a) *(f32x4*)(part + ((size_t)(b * G::NCO + a) * 64 + lane) * 4) = acc[a][s];
+      for (int a = 0; a < G::NCO; ++a) {
+        f32x4* slot = (f32x4*)(part + ((size_t)(b * G::NCO + a) * 64 + lane) * 4);
+        *slot = flushed ? *slot + acc[a][s] : acc[a][s];
+      }
     }
   }
   // ---- bias partial: sum over threads with the same channel quad ----
@@ -916,7 +948,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const dmd_wgrad_params p, in
 //              the pair of buffers is the old tile's LDS);
 // one workgroup barrier per sub-tile.  A SIMD holds one wave of each role: the staging arithmetic issues under the MFMAs.
 // Same plan (wgrad_plan: a workgroup = a contiguous range of 128-pixel tiles = sub-tiles 2 t, 2 t + 1), same partial layout,
-// same order of accumulation per accumulator element (sub-tile by sub-tile, 32 pixels per MFMA, h.l + l.h + h.h) and per bias
+// same order of accumulation per accumulator element (sub-tile by sub-tile, 32 pixels per MFMA, l.l + h.l + l.h + h.h) and per bias
 // element: with DMD_PROLOGUE_NONE the partials are BITWISE those of wgrad_kernel<G, true>; a normalised source differs in the
 // last bit of its activations (v_exp / v_rcp SiLU like the forward's split-fp16 kernels instead of expf and an IEEE division:
 // the exact form is 45 instructions per element and would make the producers the critical path).
@@ -1223,6 +1255,7 @@ __global__ __launch_bounds__(512) void wgrad_ps_kernel(const dmd_wgrad_params p,
         const wg_h8 bh = __builtin_bit_cast(wg_h8, h), bl = __builtin_bit_cast(wg_h8, l);
 #pragma unroll
         for (int a = 0; a < G::NCO; ++a) {
+          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[a], bl, acc[a][b], 0, 0, 0);
           acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[a], bl, acc[a][b], 0, 0, 0);
           acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[a], bh, acc[a][b], 0, 0, 0);
           acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[a], bh, acc[a][b], 0, 0, 0);

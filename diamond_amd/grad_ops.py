@@ -43,7 +43,9 @@ def pow2_scaled(d: Tensor) -> Tuple[Tensor, Tensor]:
     """(d * 2^k, 2^-k), k chosen on the device so that the largest entry of d * 2^k is O(1).  A backward pass is linear in the
     gradient it starts from, so it runs on the scaled one and its results are scaled back: exact in fp32, and it keeps the
     split-fp16 operands (absolute error floor 2^-25, dmd_conv_f16ws.hip) far above their floor however small the loss scale is --
-    with loss = mean over B*T the raw gradients are ~1e-6."""
+    with loss = mean over B*T the raw gradients are ~1e-6.  ONE scalar serves the whole batch and every channel: an output
+    channel whose gradient is below 2^-3 of the largest entry still meets the per-channel floor of the split-fp16 weight gradient
+    (its row of dW carries the absolute 2^-25 of its operands: include/diamond_hip.h at dmd_wgrad_params.precision has the table)."""
     d = d.detach().float()
     amax = d.abs().amax()
     k = torch.where(amax > 0, torch.floor(-torch.log2(amax.clamp_min(1e-37))), torch.zeros_like(amax)).clamp(-120, 120)

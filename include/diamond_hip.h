@@ -665,7 +665,24 @@ typedef struct dmd_wgrad_params {
   float* workspace;    /* dmd_wgrad_workspace_floats(p) floats */
   float* dw;           /* OIHW (Cout, cin_real, k, k) */
   float* dbias;        /* (Cout) or NULL */
-  int32_t precision;   /* DMD_PRECISION_F32 (exact fp32 fma chain) | DMD_PRECISION_F16X2 (split-fp16 operands, fp32 accumulate) */
+  int32_t precision;   /* DMD_PRECISION_F32 (exact fp32 fma chains of at most 2,048 pixels) | DMD_PRECISION_F16X2 (split-fp16 operands, fp32 accumulate) */
+  /* DMD_PRECISION_F16X2, the OPERAND CONTRACT (tests/test_wgrad_precision.py pins every sentence):
+   *  - both operands -- dy, and the source after its prologue -- enter as h + l, h = fp16(x), l = fp16(x - h), |x| < 65520:
+   *    |x - (h + l)| <= e(x) = max(2^-22 |x|, 2^-25); an exact zero stays exact.  The kernels sum all four products, l l + h l + l h + h h,
+   *    so ONE product is within 2^-21 |dy a| where both operands are >= 2^-3, and an element within
+   *    sum_pixels e(dy) |a| + |dy| e(a) + e(dy) e(a) of the fp32-class result.
+   *  - a FINITE operand beyond the range splits into h = inf, l = -inf: such a dy[.., co] makes the whole row dw[co][*][*] NaN,
+   *    such a source value a[.., ci] the whole column dw[*][ci][*]; every other row and column is untouched, and none is a
+   *    finite wrong number.  NaN / Inf operands do the same.  db is summed from the RAW fp32 dy on both routes: finite, fp32-class.
+   *  - PER ROW: dw[co] is a sum over pixels of dy[.., co] alone, and one scalar (grad_ops.pow2_scaled) scales the whole launch
+   *    to O(1).  A row whose dy is >= 2^-3 of that has l a normal fp16 and is fp32-class (within 30 x the fp32 reference, like
+   *    the exact route).  Below 2^-3, l is a fp16 subnormal and the operand error an ABSOLUTE 2^-25: the row's relative error
+   *    grows as the inverse of its scale.  Measured on the MI355X (profiles/wgrad_precision.txt; max |err| / max |dw| of the row,
+   *    N = 3 at 8x16, 64 -> 64 3x3, source 1.3 N(0, 1) + 0.2, wgrad_ps_kernel; the exact route stays at 1e-7 .. 7e-7 on every line):
+   *      dy channel scale   2^0     2^-4    2^-6    2^-10   2^-14   2^-20   2^-26
+   *      row error          1.5e-7  3.2e-7  8.9e-7  1.9e-5  2.7e-4  1.9e-2  0.91
+   *    An output channel at about 2^-13 (1.2e-4) of the launch's largest gradient loses the 1e-4 bar (5.4e-5 at 2^-12, 1.4e-4 at
+   *    2^-13); at 2^-26 the row is flushed. */
   /* VALID EXTENT (ABI v8; both 0: the whole tensor): rows < valid_h, columns < valid_w of src and dy exist; positions outside are
    * the convolution's zero padding (input, after the prologue) / contribute nothing (dy), GroupNorm counts the valid pixels. */
   int32_t valid_h, valid_w;
