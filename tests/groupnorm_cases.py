@@ -268,3 +268,19 @@ def act(arm: str, h: int, w: int, c: int, plus_one: bool = True, valid: Optional
     for arr in (a.x, a.mul, a.add):
         arr.setflags(write=False)
     return a
+
+
+# ---- the metric and the bounds' constants (tests/test_groupnorm_precision.py's docstring has the table; wgrad shares the backward's) ----
+K_EXACT = 16.0  # exact-fp32 forward kernels
+K_SPLIT = 10.0  # split-fp16 forward kernels
+K_BWD = 30.0    # backward kernels (against float32 CPU autograd)
+FLOOR_EXACT = 2.0 ** -24
+FLOOR_SPLIT = 2.0 ** -20  # dmd_conv_f16ws.hip's header: 3-8e-7 of the output scale per convolution
+
+
+def rows_errors(got, truth):
+    """(B, M) tensors -> (B,): max |got - truth| of a row / max |truth| of the same row, non-finite entries left out; a row whose
+    truth is zero throughout has error 0 where got is zero throughout too, else infinity"""
+    fin = lambda x: torch.where(torch.isfinite(x), x.abs(), torch.zeros_like(x)).amax(dim=1)
+    d, s = fin(got.double() - truth.double()), fin(truth.double())
+    return torch.where(s > 0, d / s.clamp_min(1e-300), torch.where(d > 0, torch.full_like(d, math.inf), torch.zeros_like(d)))

@@ -3,9 +3,9 @@ route to it (engine.attention in default precision, ATTN_F16X2_EXTENT_MIN_T / DI
 (the kernel's own source, arrays fenced: an out-of-bounds access fails there; a wave that missed a barrier is a diagnosed deadlock)
 and on the device (-m gpu).  `out` starts as NaN in every test; the margins of every extent hold NaN and +-Inf.
 
-Against float64 of the CROPPED tensors, per (image, head), every head at its own V scale (test_attention_precision.Ref):
+Against float64 of the CROPPED tensors, per (image, head), every head at its own V scale (attention_cases.Ref):
     err <= K_SPLIT x max(err_fp32, 2^-24)
-K_SPLIT is test_attention_precision's constant for the on-grid kernel, imported: the arithmetic per (query, key) pair is the same,
+K_SPLIT is attention_cases' constant for the on-grid kernel, imported: the arithmetic per (query, key) pair is the same,
 a masked key adds exactly 0.  profiles/attention_f16x2_extent_precision.txt has the measured ratios of every case below
 (`python tools/attention_fwd_bench.py --f16x2-precision` writes it).
 
@@ -14,17 +14,17 @@ short of a tile / one key into the second: a second workgroup with ONE valid que
 whole tiles and a quarter); 360 (18 x 20 of 32 x 32); 323 (17 x 19 of 32 x 32: odd row width, the second workgroup has 67 valid
 queries, two of its waves none); 1296 (36 x 36 of 64 x 64, device only).  The interpreter arm runs N = 2, C = 16, the device arm
 N = 2, C = 24 (three heads: a wrong head stride shows)."""
+import functools
 import json
 import math
 import os
 from types import SimpleNamespace
 
-import numpy as np
 import pytest
 import torch
 
-from tests import test_attention_f32_tiled as F
-from tests import test_attention_precision as P
+from tests import abi
+from tests import attention_cases as P
 
 K = P.K_SPLIT
 N = 2
@@ -36,55 +36,24 @@ PARTIAL = (32, 32, 18, 20)  # 360 tokens: a whole tile and a partial one
 ODD = (32, 32, 17, 19)      # 323 tokens
 
 
-# ---- the two runners ---------------------------------------------------------------------------------------------------------------
-def run_simt(qkv, h, w, vh, vw, c, head_dim=8, status=False):
-    from tests.simt import loader as S
-    from tests.simt.fence import fenced as G
+# ---- the two arms ------------------------------------------------------------------------------------------------------------------
+def _arm(name, run, c):
+    """`run` is dmd_attention_f16x2 on an extent (status=True: (rc, out) without raising), `attention` its flat call (N, T, 3C) ->
+    (N, T, C), the shape attention_cases' helpers expect of an arm; `other` is dmd_attention on the same runner.  Tensors"""
+    def launch(qkv, h, w, vh, vw, c, **kw):
+        got = abi.attention(run, qkv, c, "dmd_attention_f16x2", (h, w, vh, vw), **kw)
+        return (got[0], torch.from_numpy(got[2])) if kw.get("status") else torch.from_numpy(got)
 
-    a = G(qkv.contiguous().numpy())
-    out = G(np.full(tuple(qkv.shape[:-1]) + (c,), np.nan, dtype=np.float32))
-    rc = S.lib().dmd_attention_f16x2(S.ptr(a), S.ptr(out), qkv.shape[0], h, w, vh, vw, c, head_dim, None)
-    if status:
-        return rc, torch.from_numpy(np.array(out))
-    S.check(rc, "dmd_attention_f16x2")
-    return torch.from_numpy(np.array(out))
+    return SimpleNamespace(name=name, run=launch, c=c, attention=lambda qkv, c: launch(qkv, 1, qkv.shape[1], 1, qkv.shape[1], c),
+                           other=lambda qkv, c: torch.from_numpy(abi.attention_default(run, qkv, c)))
 
 
-def run_gpu(qkv, h, w, vh, vw, c, head_dim=8, status=False):
-    from diamond_amd import native as nv
-
-    a = qkv.cuda().contiguous()
-    out = torch.full(tuple(qkv.shape[:-1]) + (c,), float("nan"), device="cuda")
-    rc = nv.lib().dmd_attention_f16x2(nv.fptr(a), nv.fptr(out), qkv.shape[0], h, w, vh, vw, c, head_dim, nv.stream())
-    if status:
-        return rc, out.cpu()
-    nv.check(rc, "dmd_attention_f16x2")
-    return out.cpu()
+SIMT = _arm("simt-f16x2-extent", abi.Simt, 16)
+GPU = _arm("gpu-f16x2-extent", abi.Gpu, 24)
+BOTH = abi.arms(SIMT, GPU)
 
 
-def _arm(name, run, c, other):
-    """`attention` is the flat call (N, T, 3C) -> (N, T, C), the shape test_attention_precision's helpers expect of a runner;
-    `other` is that file's runner of the existing entry points on the same machine"""
-    return SimpleNamespace(name=name, run=run, c=c, other=other, attention=lambda qkv, c: run(qkv, 1, qkv.shape[1], 1, qkv.shape[1], c))
-
-
-SIMT = _arm("simt-f16x2-extent", run_simt, 16, P.Simt)
-GPU = _arm("gpu-f16x2-extent", run_gpu, 24, P.Gpu)
-BOTH = [pytest.param(SIMT, id="simt"), pytest.param(GPU, marks=pytest.mark.gpu, id="gpu")]
-
-
-def both(*cases, gpu_only=()):
-    out = []
-    for case in cases:
-        case = case if isinstance(case, tuple) else (case,)
-        tag = "-".join("x".join(str(v) for v in x) if isinstance(x, tuple) else str(x) for x in case)
-        out.append(pytest.param(SIMT, *case, id=f"simt-{tag}"))
-        out.append(pytest.param(GPU, *case, marks=pytest.mark.gpu, id=f"gpu-{tag}"))
-    for case in gpu_only:
-        case = case if isinstance(case, tuple) else (case,)
-        tag = "-".join("x".join(str(v) for v in x) if isinstance(x, tuple) else str(x) for x in case)
-        out.append(pytest.param(GPU, *case, marks=pytest.mark.gpu, id=f"gpu-{tag}"))
-    return out
+both = functools.partial(abi.arms, SIMT, GPU)  # both(cases): (arm, *case) on the two arms
 
 
 # ---- extents -----------------------------------------------------------------------------------------------------------------------
@@ -121,21 +90,13 @@ def on_extent(arm, flat, extent, c, fill="nonfinite"):
     return crop(out, extent)
 
 
-def ratios(ref, got):
-    e = P.head_errors(got, ref.truth, ref.vmax, ref.c)
-    return e, e / torch.maximum(ref.e32, torch.full_like(ref.e32, P.FLOOR))
+ratios = P.ratios
 
 
 def check_bound(family, arm, ref, got, what=""):
     """print the figures of the worst (image, head), then assert the bound on every (image, head)"""
     n, t, _ = ref.qkv.shape
-    e, ratio = ratios(ref, got)
-    i = int(ratio.argmax())
-    print(f"ATTF16X {arm.name} family={family}{what} tv={t} N={n} C={ref.c}: err {float(e.flatten()[i]):.3e} fp32 {float(ref.e32.flatten()[i]):.3e} "
-          f"ratio {float(ratio.max()):.2f} (largest err {float(e.max()):.3e})")
-    assert bool(torch.isfinite(got).all()), "non-finite output"
-    assert float(ratio.max()) <= K, (float(ratio.max()), ratio)
-    return float(ratio.max())
+    return P.check_bound(f"ATTF16X {arm.name} family={family}{what} tv={t} N={n} C={ref.c}", ref, got, K)[1]
 
 
 SCALES = (1.5, 4.0, 8.0, 16.0)
@@ -157,7 +118,7 @@ def tokens(extent):
     return extent[2] * extent[3]
 
 
-@pytest.mark.parametrize("arm,extent", both(*[(e,) for e in EXTENTS], gpu_only=[(e,) for e in GPU_ONLY_EXTENTS]))
+@pytest.mark.parametrize("arm,extent", both([(e,) for e in EXTENTS + GPU_ONLY_EXTENTS], simt_if=lambda e: e not in GPU_ONLY_EXTENTS))
 def test_extent_vs_fp64_of_the_cropped_tensors_with_non_finite_margins(arm, extent):
     ref = P.family_scale(N, arm.c, tokens(extent), 1.5)
     assert not bool(torch.isfinite(margin(embed(ref.qkv, extent), extent)).any())
@@ -165,7 +126,7 @@ def test_extent_vs_fp64_of_the_cropped_tensors_with_non_finite_margins(arm, exte
 
 
 # ---- the families on an extent with a partial last tile -----------------------------------------------------------------------------
-@pytest.mark.parametrize("arm,a", both(*SCALES))
+@pytest.mark.parametrize("arm,a", both(SCALES))
 def test_score_magnitude(arm, a):
     """Family 1: q, k ~ a N(0, 1): scores up to +-700 at a = 16"""
     ref = P.family_scale(N, arm.c, tokens(PARTIAL), a)
@@ -201,7 +162,7 @@ def test_onehot_and_uniform_rows(arm):
     assert bool(((got[:, ref.hot + 1].double() - mean).abs() <= lim[:, ref.hot + 1]).all()), "a q = 0 row is not the mean of V"
 
 
-@pytest.mark.parametrize("arm,which", both("v", "kv"))
+@pytest.mark.parametrize("arm,which", both(["v", "kv"]))
 def test_operands_up_to_the_end_of_fp16(arm, which):
     """Family 5: v ("v"), and k too ("kv"), reaching +-65504; "kv" has q ~ 2e-4: both workgroups rebalance"""
     ref = P.family_range(N, arm.c, tokens(PARTIAL), which)
@@ -242,15 +203,15 @@ def test_absent_queries_stay_out_of_the_rebalancing(arm):
 
 
 # ---- bitwise -----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("arm,t", both(256, 512))
+@pytest.mark.parametrize("arm,t", both([256, 512]))
 def test_whole_tile_grids_are_bitwise_dmd_attention(arm, t):
     """the extent (1, T, 1, T) with T % 256 == 0 runs the on-grid inner loops on the same operands"""
     qkv = P.family_scale(N, arm.c, t, 4.0).qkv
     got = arm.attention(qkv, arm.c)
-    assert bool(torch.isfinite(got).all()) and torch.equal(got, arm.other.attention(qkv, arm.c))
+    assert bool(torch.isfinite(got).all()) and torch.equal(got, arm.other(qkv, arm.c))
 
 
-@pytest.mark.parametrize("arm,extent", both((PARTIAL,), (ODD,), ((24, 24, 24, 24),)))
+@pytest.mark.parametrize("arm,extent", both([(PARTIAL,), (ODD,), ((24, 24, 24, 24),)]))
 def test_an_extent_is_bitwise_the_flat_call_on_the_compacted_tokens(arm, extent):
     """(H, W, vh, vw) == (1, tv, 1, tv) on the compacted tokens; with the whole grid, (H, W, H, W) == (1, H W, 1, H W)"""
     qkv = P.family_scale(N, arm.c, tokens(extent), 4.0).qkv
@@ -303,7 +264,7 @@ def test_a_finite_value_beyond_fp16_is_loud_and_confined(arm):
     assert bool(torch.isfinite(got[~touched]).all()) and not bool(torch.isfinite(got[touched]).all())
 
 
-@pytest.mark.parametrize("arm,operand", both("q", "k", "v"))
+@pytest.mark.parametrize("arm,operand", both(["q", "k", "v"]))
 def test_non_finite_operands_behave_as_in_float32(arm, operand):
     """Family 6b on the 18 x 20 extent: NaN, +Inf, -Inf in one element of q, k or v: finite exactly where the float32 CPU
     evaluation of the cropped tensors is, the finite part within the bound, everything outside the planted head / row / dim
@@ -384,25 +345,13 @@ def test_routing_switch_on_the_interpreter(monkeypatch):
     T % 256 != 0): DIAMOND_ATTN_F16X2_MIN_T=64 sends every attention forward to attention_f16x2_kernel through dmd_attention_f16x2,
     in inference and in a training step (whose backward count matches); =0 and unset give attention_kernel and a direct
     dmd_attention call's bits; DIAMOND_ATTN_PRECISION=f32 goes before it"""
-    import diamond_amd as D
     from diamond_amd import engine as E
     from diamond_amd import native as nv
-    from diamond_amd.inner_model import InnerModelConfig
-    from diamond_amd.testing import fill_module_, synthetic_actions, synthetic_frames
-    from tests import test_attention_bwd_mfma as M
-    from tests import wide_configs as W
     from tests.simt.host_harness import engine_on_interpreter
 
     assert E.ATTN_F16X2_EXTENT_MIN_T == 0 or E.ATTN_F16X2_EXTENT_MIN_T > 64
-    cfg = dict(W.DENOISER, depths=[1, 1], channels=[64, 96], attn_depths=[0, 1])
-    den = D.Denoiser(D.DenoiserConfig(inner_model=InnerModelConfig(**cfg), sigma_data=0.5, sigma_offset_noise=0.3))
-    fill_module_(den, W.WEIGHT_SEED)
-    den.setup_training(D.SigmaDistributionConfig(**W.SIGMA_DIST))
-    den.randn_fn = lambda shape: torch.randn(*shape)
-    g = torch.Generator().manual_seed(31)
-    frames, act = synthetic_frames(g, 1, 5, 3, 16, 16), synthetic_actions(g, 4, 1, 5)
-    batch = SimpleNamespace(obs=frames, act=act, mask_padding=torch.ones(1, 5, dtype=torch.bool))
-    noisy, obs = torch.randn(1, 3, 16, 16, generator=g), frames[:, :4].reshape(1, 12, 16, 16)
+    den, batch, noisy, obs = P.two_level_denoiser()
+    act = batch.act
 
     seen, names = [], []
     attention = E.attention
@@ -415,7 +364,7 @@ def test_routing_switch_on_the_interpreter(monkeypatch):
     monkeypatch.setattr(E, "attention", spy)
     variables = ("DIAMOND_ATTN_PRECISION", "DIAMOND_ATTN_F32_MIN_T", "DIAMOND_ATTN_F16X2_MIN_T", "DIAMOND_ATTN_BWD_MIN_T")
 
-    class Counter(F._Counter):
+    class Counter(P.LaunchCounter):
         def call(self, name, fn, args):
             names.append(name)
             return super().call(name, fn, args)
@@ -429,7 +378,7 @@ def test_routing_switch_on_the_interpreter(monkeypatch):
         monkeypatch.setattr(nv, "PROFILER", counter)
         del seen[:], names[:]
         out = den.compute_model_output(noisy, obs, act[:, :4], 1.3)
-        return out, {k: v for k, v in counter.n.items() if k in F.FORWARD_KEYS + ("dmd_attention_f16x2",)}, list(seen), set(names)
+        return out, {k: v for k, v in counter.n.items() if k in P.FORWARD_KEYS + ("dmd_attention_f16x2",)}, list(seen), set(names)
 
     with engine_on_interpreter():
         o_def, n_def, s_def, _ = forward({})
@@ -442,7 +391,7 @@ def test_routing_switch_on_the_interpreter(monkeypatch):
         assert attn >= 1 and n_def == {"attention_kernel": attn}, n_def
         for qkv, out, c in s_def:  # unset: a direct dmd_attention call's bits (64 tokens: attention_kernel)
             assert qkv.shape[1] * qkv.shape[2] == 64
-            assert torch.equal(out.reshape(1, 64, c), P.Simt.attention(qkv.reshape(1, 64, 3 * c), c))
+            assert torch.equal(out.reshape(1, 64, c), SIMT.other(qkv.reshape(1, 64, 3 * c), c))
         assert n_off == n_def and torch.equal(o_off, o_def) and "dmd_attention_f16x2" not in c_off
         assert n_far == n_def and torch.equal(o_far, o_def), "65 > 64 tokens"
         assert n_new == {"attention_f16x2_kernel": attn} and "dmd_attention_f16x2" in c_new and "dmd_attention" not in c_new, (n_new, c_new)
@@ -461,15 +410,15 @@ def test_routing_switch_on_the_interpreter(monkeypatch):
             monkeypatch.setenv("DIAMOND_ATTN_F16X2_MIN_T", value)
             counter = Counter()
             monkeypatch.setattr(nv, "PROFILER", counter)
-            steps[value] = (M._step(den, batch), dict(counter.n))
+            steps[value] = (P.training_step(den, batch), dict(counter.n))
         (loss, grads), n_step = steps["64"]
         (loss0, grads0), n_step0 = steps["0"]
-        fwd = {k: v for k, v in n_step.items() if k in F.FORWARD_KEYS}
+        fwd = {k: v for k, v in n_step.items() if k in P.FORWARD_KEYS}
         assert set(fwd) == {"attention_f16x2_kernel"} and n_step.get("dmd_attention_bwd", 0) == fwd["attention_f16x2_kernel"], n_step
-        assert {k: v for k, v in n_step0.items() if k in F.FORWARD_KEYS} == {"attention_kernel": fwd["attention_f16x2_kernel"]}, n_step0
+        assert {k: v for k, v in n_step0.items() if k in P.FORWARD_KEYS} == {"attention_kernel": fwd["attention_f16x2_kernel"]}, n_step0
         assert n_step0.get("dmd_attention_bwd", 0) == n_step["dmd_attention_bwd"]
         assert bool(torch.isfinite(loss)) and all(bool(torch.isfinite(v).all()) for v in grads.values())
-        M.assert_training_parity(grads, grads0)
+        P.assert_training_parity(grads, grads0)
         assert any(not torch.equal(grads[k], grads0[k]) for k in grads0), "the switch changed nothing"
 
 
@@ -483,7 +432,7 @@ def test_golden_training_step_68x76_with_the_new_route(monkeypatch):
 
     monkeypatch.setenv("DIAMOND_ATTN_F16X2_MIN_T", "256")
     monkeypatch.delenv("DIAMOND_ATTN_PRECISION", raising=False)
-    counter = F._Counter()
+    counter = P.LaunchCounter()
     monkeypatch.setattr(nv, "PROFILER", counter)
     OT.check_denoiser_training_step("denoiser_train_attn0011_68x76.pt")
     assert counter.n.get("attention_f16x2_kernel", 0) >= 2, counter.n
@@ -504,7 +453,7 @@ def test_model_output_72x72_is_within_parity_of_the_old_route(monkeypatch):
     got = {}
     for value in ("256", "0"):
         monkeypatch.setenv("DIAMOND_ATTN_F16X2_MIN_T", value)
-        counter = F._Counter()
+        counter = P.LaunchCounter()
         monkeypatch.setattr(nv, "PROFILER", counter)
         got[value] = (den.compute_model_output(noisy, obs, act, 1.3), counter.n)
     (o_new, n_new), (o_old, n_old) = got["256"], got["0"]
@@ -527,7 +476,8 @@ def test_graphed_training_step_with_the_new_route_is_bitwise_the_eager_loop(monk
     monkeypatch.delenv("DIAMOND_ATTN_PRECISION", raising=False)
     make_agent = OT.make_agent
     monkeypatch.setattr(OT, "make_agent", lambda: make_agent(attn_depths=(0, 0, 1, 0)))
-    counter = F._Counter()
+    counter = P.LaunchCounter()
     monkeypatch.setattr(nv, "PROFILER", counter)
     OT.test_graphed_training_step_72x72_is_bitwise_the_eager_loop()
     assert counter.n.get("attention_f16x2_kernel", 0) >= 1, counter.n
+

@@ -3,7 +3,7 @@ addressed by their valid index) and the switch that routes to it (engine.attenti
 `attn_precision` on the denoiser's inference and training paths), on the SIMT interpreter (the kernel's own source, arrays fenced:
 an out-of-bounds access fails there) and on the device (-m gpu).  `out` starts as NaN in every test.
 
-Against float64, per (image, head), every head at its own V scale (test_attention_precision.Ref / head_errors):
+Against float64, per (image, head), every head at its own V scale (attention_cases.Ref / head_errors):
     err <= K_TILED x max(err_fp32, 2^-24)
 K_TILED = twice the largest ratio measured on the MI355X over every case of this file (profiles/attention_f32_tiled_precision.txt
 has the table; `python tools/attention_fwd_bench.py --precision` writes it and applies this rule): 2 x 4.7732 rounded up (scaled family, a = 16, T = 320, C = 24,
@@ -18,12 +18,11 @@ import functools
 import math
 from types import SimpleNamespace
 
-import numpy as np
 import pytest
 import torch
 
-from tests import test_attention_bwd_valid as V
-from tests import test_attention_precision as P
+from tests import abi
+from tests import attention_cases as P
 
 K_TILED = 9.55  # 2 x 4.7732, rounded up to two decimals (tools/attention_fwd_bench.py k_tiled)
 assert K_TILED <= P.K_EXACT
@@ -32,69 +31,38 @@ TS = (64, 80, 256, 320, 512, 768, 1024)
 N = 2
 
 
-# ---- the two runners ---------------------------------------------------------------------------------------------------------------
-def run_simt(qkv, h, w, vh, vw, c):
-    from tests.simt import loader as S
-    from tests.simt.fence import fenced as G
-
-    a = G(qkv.contiguous().numpy())
-    out = G(np.full(tuple(qkv.shape[:-1]) + (c,), np.nan, dtype=np.float32))
-    S.check(S.lib().dmd_attention_f32(S.ptr(a), S.ptr(out), qkv.shape[0], h, w, vh, vw, c, 8, None), "dmd_attention_f32")
-    return torch.from_numpy(np.array(out))
+# ---- the two arms ------------------------------------------------------------------------------------------------------------------
+def _arm(name, run, c, entry="dmd_attention_f32"):
+    """`run` is the entry point on an extent, `attention` its flat call (N, T, 3C) -> (N, T, C), the shape attention_cases' helpers
+    expect of an arm; `other` is dmd_attention (exact=True: attention_kernel) on the same runner.  All return tensors"""
+    launch = lambda qkv, h, w, vh, vw, c, **kw: torch.from_numpy(abi.attention(run, qkv, c, entry, (h, w, vh, vw), **kw))
+    return SimpleNamespace(name=name, run=launch, c=c, attention=lambda qkv, c: launch(qkv, 1, qkv.shape[1], 1, qkv.shape[1], c),
+                           other=lambda qkv, c, exact=False: torch.from_numpy(abi.attention_default(run, qkv, c, exact)))
 
 
-def run_gpu(qkv, h, w, vh, vw, c):
-    from diamond_amd import native as nv
-
-    a = qkv.cuda().contiguous()
-    out = torch.full(tuple(qkv.shape[:-1]) + (c,), float("nan"), device="cuda")
-    nv.check(nv.lib().dmd_attention_f32(nv.fptr(a), nv.fptr(out), qkv.shape[0], h, w, vh, vw, c, 8, nv.stream()), "dmd_attention_f32")
-    return out.cpu()
+SIMT = _arm("simt-f32", abi.Simt, 16)
+GPU = _arm("gpu-f32", abi.Gpu, 24)
+BOTH = abi.arms(SIMT, GPU)
 
 
-def _arm(name, run, c, other):
-    """`attention` is the flat call (N, T, 3C) -> (N, T, C), in the shape test_attention_precision's helpers expect of a runner;
-    `other` is that file's runner of the existing kernels on the same machine"""
-    return SimpleNamespace(name=name, run=run, c=c, other=other, attention=lambda qkv, c: run(qkv, 1, qkv.shape[1], 1, qkv.shape[1], c))
-
-
-SIMT = _arm("simt-f32", run_simt, 16, P.Simt)
-GPU = _arm("gpu-f32", run_gpu, 24, P.Gpu)
-
-
-def arms(*more, ts=TS, wide=True, simt_max_t=512):
+def arms(*more, ts=TS, wide=True):
     """(arm, t, c, *extra) cases: the interpreter arm gets T <= 512 only, the device arm every T and (wide) C = 64 at T = 1280"""
     extras = [()] if not more else [e if isinstance(e, tuple) else (e,) for e in more]
-    out = []
-    for t, c in [(t, None) for t in ts] + ([(1280, 64)] if wide else []):
-        for e in extras:
-            tag = "-".join([str(t)] + ([f"c{c}"] if c else []) + [str(x) for x in e])
-            if c is None and t <= simt_max_t:
-                out.append(pytest.param(SIMT, t, SIMT.c, *e, id=f"simt-{tag}"))
-            out.append(pytest.param(GPU, t, c or GPU.c, *e, marks=pytest.mark.gpu, id=f"gpu-{tag}"))
-    return out
-
-
-BOTH = [pytest.param(SIMT, id="simt"), pytest.param(GPU, marks=pytest.mark.gpu, id="gpu")]
+    cases = [(t, c) + e for t, c in [(t, None) for t in ts] + ([(1280, 64)] if wide else []) for e in extras]
+    return abi.arms(SIMT, GPU, cases, simt_if=lambda t, c, *e: c is None and t <= 512,
+                    tag=lambda t, c, *e: "-".join([str(t)] + ([f"c{c}"] if c else []) + [str(x) for x in e]),
+                    values=lambda arm, t, c, *e: (t, c or arm.c) + e)
 
 
 # ---- the bound ---------------------------------------------------------------------------------------------------------------------
-def ratios(ref, got):
-    """(error, error / max(err_fp32, 2^-24)) per (image, head)"""
-    e = P.head_errors(got, ref.truth, ref.vmax, ref.c)
-    return e, e / torch.maximum(ref.e32, torch.full_like(ref.e32, P.FLOOR))
+ratios = P.ratios
 
 
 def check_bound(family, arm, ref, got, what=""):
     """print the figures of the worst (image, head), then assert the bound on every (image, head)"""
     n, t, _ = ref.qkv.shape
-    e, ratio = ratios(ref, got)
-    i = int(ratio.argmax())
-    print(f"ATTF32 {arm.name} family={family}{what} T={t} N={n} C={ref.c}: err {float(e.flatten()[i]):.3e} fp32 {float(ref.e32.flatten()[i]):.3e} "
-          f"ratio {float(ratio.max()):.2f} (largest err {float(e.max()):.3e})")
-    assert bool(torch.isfinite(got).all()), "non-finite output"
-    assert float(ratio.max()) <= K_TILED, (float(ratio.max()), ratio)
-    return float(ratio.max())
+    return P.check_bound(f"ATTF32 {arm.name} family={family}{what} T={t} N={n} C={ref.c}", ref, got, K_TILED)[1]
+
 
 
 SCALES = (1.5, 4.0, 8.0, 16.0)
@@ -206,7 +174,7 @@ def test_a_finite_value_beyond_fp16_is_simply_computed(arm):
     t, c = 256, arm.c
     ref, where = beyond_fp16_case(t, c)
     qkv = ref.qkv
-    default = arm.other.attention(qkv, c)
+    default = arm.other(qkv, c)
     touched = torch.zeros(N, t, c, dtype=torch.bool)
     (ki, kh, _, _), (vi, vh_, _, vd) = where["k"], where["v"]
     touched[ki, :, 8 * kh:8 * kh + 8] = True
@@ -221,25 +189,16 @@ def test_a_finite_value_beyond_fp16_is_simply_computed(arm):
 @functools.lru_cache(maxsize=None)
 def extent_inputs(h, w, vh, vw):
     """qkv (N, H, W, 3C) with NaN / 3e38 margins and the Ref of the cropped tensors"""
-    qkv, _, _, _, inside = V.make_inputs(h, w, vh, vw, seed=h + vh + vw)
-    return qkv, P.Ref(qkv[:, :vh, :vw].reshape(V.N, vh * vw, 3 * V.C).contiguous(), V.C), inside
+    qkv, _, _, _, inside = P.extent_inputs(h, w, vh, vw, seed=h + vh + vw)
+    return qkv, P.Ref(qkv[:, :vh, :vw].reshape(P.EXTENT_N, vh * vw, 3 * P.EXTENT_C).contiguous(), P.EXTENT_C), inside
 
 
-def extent_arms():
-    out = []
-    for case in V.CASES:
-        tag = "x".join(str(x) for x in case)
-        out.append(pytest.param(SIMT, *case, id=f"simt-{tag}"))
-        out.append(pytest.param(GPU, *case, marks=pytest.mark.gpu, id=f"gpu-{tag}"))
-    return out
-
-
-@pytest.mark.parametrize("arm,h,w,vh,vw", extent_arms())
+@pytest.mark.parametrize("arm,h,w,vh,vw", abi.arms(SIMT, GPU, P.EXTENT_CASES, tag=abi.joined_by_x))
 def test_valid_extent_vs_fp64_of_the_cropped_tensors_with_garbage_margins(arm, h, w, vh, vw):
     qkv, ref, inside = extent_inputs(h, w, vh, vw)
     assert not bool(torch.isfinite(qkv[:, ~inside]).all())
-    out = arm.run(qkv, h, w, vh, vw, V.C)
-    check_bound("extent", arm, ref, out[:, :vh, :vw].reshape(V.N, vh * vw, V.C), what=f" {h}x{w}/{vh}x{vw}")
+    out = arm.run(qkv, h, w, vh, vw, P.EXTENT_C)
+    check_bound("extent", arm, ref, out[:, :vh, :vw].reshape(P.EXTENT_N, vh * vw, P.EXTENT_C), what=f" {h}x{w}/{vh}x{vw}")
     margin = out[:, ~inside]
     assert bool((margin == 0).all()) and not bool(torch.signbit(margin).any()), "out outside the valid extent is not +0"
 
@@ -258,7 +217,7 @@ def test_rejects_an_extent_outside_the_grid(arm):
     qkv, _, _ = extent_inputs(16, 16, 9, 9)
     for vh, vw in ((17, 9), (9, 17), (0, 9)):
         with pytest.raises(RuntimeError, match="valid extent"):
-            arm.run(qkv, 16, 16, vh, vw, V.C)
+            arm.run(qkv, 16, 16, vh, vw, P.EXTENT_C)
 
 
 # ---- invariance --------------------------------------------------------------------------------------------------------------------
@@ -267,8 +226,8 @@ def test_two_launches_are_bitwise_equal():
     """N = 4, C = 64, T = 1024: more workgroups than CUs"""
     n, c, t = 4, 64, 1024
     qkv = torch.randn(n, t, 3 * c, generator=torch.Generator().manual_seed(12)) * 1.5
-    first = run_gpu(qkv, 1, t, 1, t, c)
-    assert bool(torch.isfinite(first).all()) and torch.equal(first, run_gpu(qkv, 1, t, 1, t, c))
+    first = GPU.run(qkv, 1, t, 1, t, c)
+    assert bool(torch.isfinite(first).all()) and torch.equal(first, GPU.run(qkv, 1, t, 1, t, c))
 
 
 @pytest.mark.parametrize("arm", BOTH)
@@ -291,7 +250,7 @@ def test_agrees_with_attention_kernel_within_the_two_bounds(arm, t, c, family):
     """the online-softmax kernel (dmd_attention_valid over the whole grid) on the same inputs: within the sum of the two bounds,
     and not the same bits (another summation order, expf against exp2)"""
     ref = P.family_scale(N, c, t, 8.0) if family == 1 else P.family_offset(N, c, t)
-    got, exact = arm.attention(ref.qkv, c), arm.other.attention(ref.qkv, c, exact=True)
+    got, exact = arm.attention(ref.qkv, c), arm.other(ref.qkv, c, exact=True)
     assert bool(torch.isfinite(got).all()) and bool(torch.isfinite(exact).all())
     both = ref.per_element(ref.limit(K_TILED) + ref.limit(P.K_EXACT))
     assert bool(((got.double() - exact.double()).abs() <= both).all()), "the two exact kernels disagree by more than their bounds"
@@ -319,49 +278,17 @@ def test_default_threshold_follows_from_the_recorded_table():
 
 
 # ---- routing on the interpreter ----------------------------------------------------------------------------------------------------
-class _Counter:
-    """stands in for native.PROFILER: counts launches per key (no timing)"""
-
-    def __init__(self):
-        self.n = {}
-        self._pending = None
-
-    def annotate(self, key, flops, nbytes):
-        self._pending = key
-
-    def call(self, name, fn, args):
-        key, self._pending = self._pending or name, None
-        self.n[key] = self.n.get(key, 0) + 1
-        return fn(*args)
-
-
-FORWARD_KEYS = ("attention_kernel", "attention_f16x2_kernel", "attention_f32_tiled_kernel", "dmd_attention", "dmd_attention_valid",
-                "dmd_attention_f32")
-
-
 def test_routing_switch_on_the_interpreter(monkeypatch):
     """the two-level network of tests/test_simt_host.py (attention over 64 tokens at its 8x8 level), inference forward and a
     training step: DIAMOND_ATTN_PRECISION=f32 with DIAMOND_ATTN_F32_MIN_T=64 sends every attention forward to
     attention_f32_tiled_kernel, =0 to attention_kernel; the attn_precision="f32" keyword alone does what the variable does; with
     the switches unset the launches and the bits are a direct dmd_attention call's"""
-    import diamond_amd as D
     from diamond_amd import engine as E
     from diamond_amd import native as nv
-    from diamond_amd.inner_model import InnerModelConfig
-    from diamond_amd.testing import fill_module_, synthetic_actions, synthetic_frames
-    from tests import test_attention_bwd_mfma as M
-    from tests import wide_configs as W
     from tests.simt.host_harness import engine_on_interpreter
 
-    cfg = dict(W.DENOISER, depths=[1, 1], channels=[64, 96], attn_depths=[0, 1])
-    den = D.Denoiser(D.DenoiserConfig(inner_model=InnerModelConfig(**cfg), sigma_data=0.5, sigma_offset_noise=0.3))
-    fill_module_(den, W.WEIGHT_SEED)
-    den.setup_training(D.SigmaDistributionConfig(**W.SIGMA_DIST))
-    den.randn_fn = lambda shape: torch.randn(*shape)
-    g = torch.Generator().manual_seed(31)
-    frames, act = synthetic_frames(g, 1, 5, 3, 16, 16), synthetic_actions(g, 4, 1, 5)
-    batch = SimpleNamespace(obs=frames, act=act, mask_padding=torch.ones(1, 5, dtype=torch.bool))
-    noisy, obs = torch.randn(1, 3, 16, 16, generator=g), frames[:, :4].reshape(1, 12, 16, 16)
+    den, batch, noisy, obs = P.two_level_denoiser()
+    act = batch.act
 
     seen = []
     attention = E.attention
@@ -378,11 +305,11 @@ def test_routing_switch_on_the_interpreter(monkeypatch):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
-        counter = _Counter()
+        counter = P.LaunchCounter()
         monkeypatch.setattr(nv, "PROFILER", counter)
         del seen[:]
         out = den.compute_model_output(noisy, obs, act[:, :4], 1.3, **kw)
-        return out, {k: v for k, v in counter.n.items() if k in FORWARD_KEYS}, list(seen)
+        return out, {k: v for k, v in counter.n.items() if k in P.FORWARD_KEYS}, list(seen)
 
     with engine_on_interpreter():
         o_def, n_def, s_def = forward({})
@@ -396,7 +323,7 @@ def test_routing_switch_on_the_interpreter(monkeypatch):
         assert attn >= 1 and n_def == {"attention_kernel": attn}, n_def
         for qkv, out, c in s_def:  # the default route: a direct dmd_attention call's bits (64 tokens: attention_kernel)
             assert qkv.shape[1] * qkv.shape[2] == 64
-            assert torch.equal(out.reshape(1, 64, c), P.Simt.attention(qkv.reshape(1, 64, 3 * c), c))
+            assert torch.equal(out.reshape(1, 64, c), SIMT.other(qkv.reshape(1, 64, 3 * c), c))
         assert n_new == {"attention_f32_tiled_kernel": attn}, n_new
         assert n_old == {"attention_kernel": attn}, n_old
         assert n_kw == n_new and torch.equal(o_kw, o_new)
@@ -410,10 +337,10 @@ def test_routing_switch_on_the_interpreter(monkeypatch):
         monkeypatch.delenv("DIAMOND_ATTN_BWD_MIN_T", raising=False)
         monkeypatch.setenv("DIAMOND_ATTN_PRECISION", "f32")
         monkeypatch.setenv("DIAMOND_ATTN_F32_MIN_T", "64")
-        counter = _Counter()
+        counter = P.LaunchCounter()
         monkeypatch.setattr(nv, "PROFILER", counter)
-        loss, grads = M._step(den, batch)
-        fwd = {k: v for k, v in counter.n.items() if k in FORWARD_KEYS}
+        loss, grads = P.training_step(den, batch)
+        fwd = {k: v for k, v in counter.n.items() if k in P.FORWARD_KEYS}
         assert set(fwd) == {"attention_f32_tiled_kernel"} and counter.n.get("dmd_attention_bwd", 0) == fwd["attention_f32_tiled_kernel"], counter.n
         assert bool(torch.isfinite(loss)) and all(bool(torch.isfinite(v).all()) for v in grads.values())
 
@@ -429,17 +356,16 @@ def _long_attention_records(tape):
 def test_model_output_with_exact_attention_is_within_parity_of_the_default_route(monkeypatch):
     """the 1024-token denoiser of test_attention_bwd_mfma, batch 2: other bits, within the contract's 1e-4 of max |output|"""
     from diamond_amd import native as nv
-    from tests import test_attention_bwd_mfma as M
 
     monkeypatch.setenv("DIAMOND_ATTN_F32_MIN_T", "1024")
     monkeypatch.delenv("DIAMOND_ATTN_PRECISION", raising=False)
-    den = M._device_denoiser().eval()
+    den = P.device_denoiser().eval()
     g = torch.Generator().manual_seed(5)
     noisy, obs = torch.randn(2, 3, 64, 64, generator=g).cuda(), torch.randn(2, 12, 64, 64, generator=g).clamp(-1, 1).cuda()
     act = torch.randint(0, 4, (2, 4), generator=g).cuda()
     got = {}
     for name, kw in (("default", {}), ("f32", {"attn_precision": "f32"})):
-        counter = _Counter()
+        counter = P.LaunchCounter()
         monkeypatch.setattr(nv, "PROFILER", counter)
         got[name] = (den.compute_model_output(noisy, obs, act, 1.3, **kw), counter.n)
     (o_def, n_def), (o_new, n_new) = got["default"], got["f32"]
@@ -458,12 +384,11 @@ def test_training_step_with_the_exact_forward(monkeypatch):
     bitwise a direct dmd_attention_f32 call on the recorded qkv"""
     from diamond_amd import native as nv
     from diamond_amd import unet_train as UT
-    from tests import test_attention_bwd_mfma as M
 
     monkeypatch.setenv("DIAMOND_ATTN_F32_MIN_T", "1024")
-    den = M._device_denoiser()
+    den = P.device_denoiser()
     den.randn_fn = lambda shape: torch.randn(*shape)
-    batch = M._device_batches(1)[0]
+    batch = P.device_batches(1)[0]
     checked = []
     backward_tape = UT.backward_tape
 
@@ -484,9 +409,9 @@ def test_training_step_with_the_exact_forward(monkeypatch):
         else:
             monkeypatch.setenv("DIAMOND_ATTN_PRECISION", value)
             monkeypatch.setattr(UT, "backward_tape", spy)
-        counter = _Counter()
+        counter = P.LaunchCounter()
         monkeypatch.setattr(nv, "PROFILER", counter)
-        got[value] = (M._step(den, batch), counter.n)
+        got[value] = (P.training_step(den, batch), counter.n)
     (l_new, g_new), n_new = got["f32"]
     (l_old, g_old), n_old = got[None]
     long_t = n_old.get("attention_f16x2_kernel", 0)
@@ -505,11 +430,11 @@ def test_graphed_training_step_with_the_switch_on_is_bitwise_the_eager_loop(monk
     """test_attention_bwd_mfma's graphed-step test with every attention forward exact: the new launch records into the hipGraph
     like the others (no allocation, no synchronisation, the variables read at capture)"""
     from diamond_amd import native as nv
-    from tests import test_attention_bwd_mfma as M
 
     monkeypatch.setenv("DIAMOND_ATTN_PRECISION", "f32")
     monkeypatch.setenv("DIAMOND_ATTN_F32_MIN_T", "1024")
-    counter = _Counter()
+    counter = P.LaunchCounter()
     monkeypatch.setattr(nv, "PROFILER", counter)
-    M.test_graphed_training_step_on_the_new_route_is_bitwise_the_eager_loop(monkeypatch)
+    P.check_graphed_training_step_is_bitwise_the_eager_loop(monkeypatch)
     assert counter.n.get("attention_f32_tiled_kernel", 0) >= 1 and "attention_f16x2_kernel" not in counter.n, counter.n
+

@@ -16,9 +16,10 @@ import functools
 import os
 from types import SimpleNamespace
 
-import numpy as np
 import pytest
 import torch
+
+from tests import abi
 
 K_DGRAD = 6.60  # 2 x 3.30, profiles/dgrad_input_precision.txt
 
@@ -45,79 +46,19 @@ def case(h, w, valid, cout, cin, n=N, margin=float("nan")):
     return dy.contiguous(), wt, want, f32
 
 
-def _fill(p, n, h, w, valid, cout, cin, c_split, stride_a, scale_b, swap):
-    p.N, p.H, p.W, p.Cout, p.cin, p.c_split = n, h, w, cout, cin, c_split
-    if valid is not None:
-        p.valid_h, p.valid_w = valid
-    p.stride_a, p.scale_b, p.swap_scales = stride_a, scale_b, int(swap)
+def _arm(run):
+    """`run` is tests/abi.py's dgrad_input with tensors for its arrays; rc=True: (status, message) of a refused launch"""
+    def launch(*args, rc=False, **kw):
+        got = abi.dgrad_input(run, *args, status=rc, **kw)
+        return got[:2] if rc else tuple(None if a is None else torch.from_numpy(a) for a in got)
+
+    return SimpleNamespace(name=run.name, run=launch)
 
 
-def run_simt(dy, wt, cin, c_split, valid=None, scale_a=None, scale_b=1.0, post=None, swap=False, want_a=True, want_b=True, rc=False):
-    from diamond_amd import native as nv
-    from tests.simt import loader as S
-    from tests.simt.fence import fenced as F
+SIMT, GPU = _arm(abi.Simt), _arm(abi.Gpu)
+BOTH = abi.arms(SIMT, GPU)
+arms = functools.partial(abi.arms, SIMT, GPU)
 
-    L = S.lib()
-    n, h, w, cout = dy.shape
-    vh, vw = valid or (h, w)
-    vh, vw = min(vh, h), min(vw, w)  # (the refused-argument test asks for more than the buffer: the outputs stay inside it)
-    keep = [F(dy.contiguous().numpy()), F(wt.contiguous().numpy())]
-    dx_a = F(np.full((n, c_split, vh, vw), np.nan, dtype=np.float32)) if want_a and c_split > 0 else None
-    dx_b = F(np.full((n, max(cin - c_split, 0), vh, vw), np.nan, dtype=np.float32)) if want_b and cin > c_split else None
-    p = nv.DgradInputParams()
-    _fill(p, n, h, w, valid, cout, cin, c_split, 0, scale_b, swap)
-    p.dy, p.w, p.dx_a, p.dx_b = S.ptr(keep[0]), S.ptr(keep[1]), S.ptr(dx_a), S.ptr(dx_b)
-    if scale_a is not None:
-        keep.append(F(scale_a.contiguous().numpy()))
-        p.scale_a, p.stride_a = S.ptr(keep[-1]), int(scale_a.numel() > 1)
-    if post is not None:
-        keep.append(F(np.array([post], dtype=np.float32)))
-        p.post = S.ptr(keep[-1])
-    code = L.dmd_conv2d_dgrad_input(ctypes.byref(p), None)
-    if rc:
-        return code, L.dmd_last_error().decode()
-    S.check(code, "dmd_conv2d_dgrad_input")
-    return tuple(None if a is None else torch.from_numpy(np.array(a)) for a in (dx_a, dx_b))
-
-
-def run_gpu(dy, wt, cin, c_split, valid=None, scale_a=None, scale_b=1.0, post=None, swap=False, want_a=True, want_b=True, rc=False):
-    from diamond_amd import native as nv
-
-    n, h, w, cout = dy.shape
-    vh, vw = valid or (h, w)
-    vh, vw = min(vh, h), min(vw, w)
-    keep = [dy.cuda().contiguous(), wt.cuda().contiguous()]
-    dx_a = torch.full((n, c_split, vh, vw), float("nan"), device="cuda") if want_a and c_split > 0 else None
-    dx_b = torch.full((n, max(cin - c_split, 0), vh, vw), float("nan"), device="cuda") if want_b and cin > c_split else None
-    p = nv.DgradInputParams()
-    _fill(p, n, h, w, valid, cout, cin, c_split, 0, scale_b, swap)
-    p.dy, p.w, p.dx_a, p.dx_b = nv.fptr(keep[0]), nv.fptr(keep[1]), nv.fptr(dx_a), nv.fptr(dx_b)
-    if scale_a is not None:
-        keep.append(scale_a.cuda().contiguous())
-        p.scale_a, p.stride_a = nv.fptr(keep[-1]), int(scale_a.numel() > 1)
-    if post is not None:
-        keep.append(torch.tensor([post], device="cuda"))
-        p.post = nv.fptr(keep[-1])
-    code = nv.lib().dmd_conv2d_dgrad_input(ctypes.byref(p), nv.stream())
-    if rc:
-        return code, nv.lib().dmd_last_error().decode()
-    nv.check(code, "dmd_conv2d_dgrad_input")
-    torch.cuda.synchronize()
-    return tuple(None if a is None else a.cpu() for a in (dx_a, dx_b))
-
-
-SIMT = SimpleNamespace(name="simt", run=run_simt)
-GPU = SimpleNamespace(name="gpu", run=run_gpu)
-BOTH = [pytest.param(SIMT, id="simt"), pytest.param(GPU, marks=pytest.mark.gpu, id="gpu")]
-
-
-def arms(cases):
-    out = []
-    for c in cases:
-        tag = "-".join("x".join(str(v) for v in x) if isinstance(x, tuple) else str(x) for x in c)
-        out.append(pytest.param(SIMT, *c, id=f"simt-{tag}"))
-        out.append(pytest.param(GPU, *c, marks=pytest.mark.gpu, id=f"gpu-{tag}"))
-    return out
 
 
 def joined(dx_a, dx_b):
@@ -183,8 +124,8 @@ def test_two_runs_are_bitwise_equal_at_the_training_shape():
     """N = 32, 64x64, Cout = 64, 15 channels: 256 workgroups"""
     g = torch.Generator().manual_seed(4)
     dy, wt = torch.randn(32, 64, 64, 64, generator=g), torch.randn(64, 15, 3, 3, generator=g) * 0.3
-    first = joined(*run_gpu(dy, wt, 15, 12))
-    assert bool(torch.isfinite(first).all()) and torch.equal(first, joined(*run_gpu(dy, wt, 15, 12)))
+    first = joined(*GPU.run(dy, wt, 15, 12))
+    assert bool(torch.isfinite(first).all()) and torch.equal(first, joined(*GPU.run(dy, wt, 15, 12)))
     want = torch.nn.functional.conv_transpose2d(dy[:2].permute(0, 3, 1, 2).double(), wt.double(), padding=1)
     assert rel_err(first[:2], want) <= 1e-5
 

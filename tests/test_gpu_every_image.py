@@ -532,7 +532,7 @@ ATT_N, ATT_C = 23, 64
 
 def attention_ref64(qkv):
     """softmax(q k^T / sqrt(8)) v per head in float64 on the CPU, image by image: (n, T, 3C) -> (n, T, C)"""
-    from tests.test_attention_precision import formula
+    from tests.attention_cases import formula
 
     return formula(qkv.cpu(), ATT_C, torch.float64)
 
@@ -587,7 +587,7 @@ def test_attention_every_image(name, grid, extent, precision, entry, kernel, mon
 
 def attention_bwd_ref64(qkv, dy):
     """float64 autograd of the softmax formula, image by image: (n, T, 3C), (n, T, C) -> dqkv (n, T, 3C)"""
-    from tests.test_attention_precision import formula
+    from tests.attention_cases import formula
 
     outs = []
     for x, d in zip(qkv.double().cpu(), dy.double().cpu()):

@@ -58,7 +58,6 @@ groups per image; 32 -> 64 would have one).
 What the interpreter cannot reproduce: expf / exp2f are the host libm's, v_rcp_f32 is an IEEE division there, and the order of
 the sums inside an MFMA is its own -- the split-fp16 prologue rows differ by up to 3x between the runners for that reason.  The
 epilogue's float32 partial sums and every float64 sum are the same bits on both: the two findings read the same on either."""
-import ctypes as C
 import functools
 import math
 
@@ -66,182 +65,15 @@ import numpy as np
 import pytest
 import torch
 
-from diamond_amd import native as nv  # struct layouts and the signature table only
+from diamond_amd import native as nv  # struct layouts only
 from tests import groupnorm_cases as GC
+from tests.abi import RUNNERS, act_norm, check, kernel_sums, launch_conv, launch_gn_silu_bwd, launch_lowres_chain, nan_like, norm_struct
+from tests.groupnorm_cases import FLOOR_EXACT, FLOOR_SPLIT, K_BWD, K_EXACT, K_SPLIT, rows_errors
 
-K_EXACT = 16.0  # exact-fp32 forward kernels
-K_SPLIT = 10.0  # split-fp16 forward kernels
-K_BWD = 30.0    # backward kernels (against float32 CPU autograd)
-FLOOR_EXACT = 2.0 ** -24
-FLOOR_SPLIT = 2.0 ** -20  # dmd_conv_f16ws.hip's header: 3-8e-7 of the output scale per convolution
 STATS_TOL = 1e-9
 
 
-# ---- the two runners: the same C ABI, on fenced host arrays (interpreter build) and on device tensors --------------------------------
-class Simt:
-    """the kernels' own source on the interpreter, arrays fenced"""
-    name = "simt"
-
-    @staticmethod
-    def lib():
-        from tests.simt import loader as S
-        return S.lib()
-
-    @staticmethod
-    def put(a):
-        from tests.simt.fence import fenced
-        return None if a is None else fenced(np.ascontiguousarray(a))
-
-    @staticmethod
-    def ptr(h):
-        return None if h is None else h.ctypes.data
-
-    @staticmethod
-    def get(h):
-        return np.array(h)
-
-    @staticmethod
-    def stream():
-        return None
-
-
-class Gpu:
-    name = "gpu"
-
-    @staticmethod
-    def lib():
-        return nv.lib()
-
-    @staticmethod
-    def put(a):
-        return None if a is None else torch.tensor(np.asarray(a)).cuda()
-
-    @staticmethod
-    def ptr(h):
-        return None if h is None else h.data_ptr()
-
-    @staticmethod
-    def get(h):
-        return h.cpu().numpy()
-
-    @staticmethod
-    def stream():
-        return nv.stream()
-
-
-RUNNERS = [pytest.param(Simt, id="simt"), pytest.param(Gpu, marks=pytest.mark.gpu, id="gpu")]
-
-
-def check(run, rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed (rc={rc}): {run.lib().dmd_last_error().decode()}")
-
-
-def nan_like(shape, dtype=np.float32):
-    return np.full(shape, np.nan, dtype=dtype)
-
-
-# ---- launches ----------------------------------------------------------------------------------------------------------------------
-def kernel_sums(run, x, hv=None, wv=None):
-    """(N, G, 1, 2) sums of dmd_gn_stats / dmd_gn_stats_valid (gn_stats_kernel; gn_stats_any_kernel for the general groups)"""
-    n, h, w, c = x.shape
-    xd, st = run.put(x), run.put(nan_like((n, GC.groups_of(c), 1, 2), np.float64))
-    if hv is None:
-        check(run, run.lib().dmd_gn_stats(run.ptr(xd), run.ptr(st), n, h * w, c, run.stream()), "dmd_gn_stats")
-    else:
-        check(run, run.lib().dmd_gn_stats_valid(run.ptr(xd), run.ptr(st), n, h, w, hv, wv, c, run.stream()), "dmd_gn_stats_valid")
-    return run.get(st)
-
-
-def norm_struct(run, keep, stats, mul, add, plus_one):
-    hs = [run.put(a) for a in (stats, mul, add)]
-    keep += hs
-    n = nv.Norm()
-    n.stats, n.stat_tiles, n.mul_plus_one = run.ptr(hs[0]), stats.shape[2], int(plus_one)
-    n.mul, n.add = run.ptr(hs[1]), run.ptr(hs[2])
-    n.mul_stride = 0 if mul is None else mul.shape[-1]
-    n.add_stride = 0 if add is None else add.shape[-1]
-    return n
-
-
-def act_norm(run, keep, a, stats=None):
-    """the dmd_norm of an activation of the cases file, statistics from the statistics kernel unless given"""
-    if stats is None:
-        stats = kernel_sums(run, a.x, *((a.hv, a.wv) if (a.hv, a.wv) != (a.h, a.w) else ()))
-    return norm_struct(run, keep, stats, a.mul, a.add, a.plus_one)
-
-
-def pack_f32(run, keep, w, cout_pad):
-    cout, cin, k, _ = w.shape
-    src, dst = run.put(w), run.put(nan_like((cin // 16) * k * k * cout_pad * 16))
-    keep += [src, dst]
-    check(run, run.lib().dmd_pack_conv_weight(run.ptr(src), run.ptr(dst), cout, cin, k, cout_pad, cin, run.stream()), "dmd_pack_conv_weight")
-    return dst
-
-
-def pack_f16(run, keep, w):
-    cout, cin, k, _ = w.shape
-    src, dst = run.put(w), run.put(np.zeros((cin // 16) * k * k * 2 * cout * 16, dtype=np.float16))
-    keep += [src, dst]
-    check(run, run.lib().dmd_pack_conv_weight_f16x2(run.ptr(src), run.ptr(dst), cout, cin, k, cin, run.stream()), "dmd_pack_conv_weight_f16x2")
-    return dst
-
-
-def launch_conv(run, srcs, w, bias, *, precision=0, w16=False, residual=None, residual_norm=None, want_stats=False, proj=None,
-                expect=None):
-    """dmd_conv2d.  srcs: [(x NHWC float32, prologue, dmd_norm builder or None)]; residual_norm: an Act whose x is the residual;
-    proj: (j0, j1, wp, bp).  Returns (out NHWC, out_stats or None)."""
-    L, keep = run.lib(), []
-    n, h, wd, _ = srcs[0][0].shape
-    cout, cin, k, _ = w.shape
-    p = nv.ConvParams()
-    p.N, p.H, p.W, p.Cout, p.CoutPad, p.taps, p.stride, p.upsample, p.nsrc, p.precision = n, h, wd, cout, cout, k * k, 1, 0, len(srcs), precision
-    for i, (x, prologue, norm) in enumerate(srcs):
-        xd = run.put(x)
-        keep.append(xd)
-        p.src[i].x, p.src[i].C, p.src[i].prologue = run.ptr(xd), x.shape[-1], prologue
-        if prologue:
-            p.src[i].norm = norm(run, keep)
-    bd = run.put(bias)
-    keep.append(bd)
-    p.w, p.bias = run.ptr(pack_f32(run, keep, w, cout)), run.ptr(bd)
-    if w16:
-        p.w_f16 = run.ptr(pack_f16(run, keep, w))
-    if residual is not None:
-        rd = run.put(residual)
-        keep.append(rd)
-        p.residual = run.ptr(rd)
-    if residual_norm is not None:
-        rd = run.put(residual_norm.x)
-        keep.append(rd)
-        p.residual = run.ptr(rd)
-        p.residual_norm = act_norm(run, keep, residual_norm)
-    if proj is not None:
-        j0, j1, wp, bp = proj
-        hs = [run.put(j0), run.put(j1), run.put(bp)]
-        keep += hs
-        p.proj_nsrc, p.proj_C[0], p.proj_C[1] = 2, 64, 64
-        p.proj_x[0], p.proj_x[1], p.proj_w_f16, p.proj_bias = run.ptr(hs[0]), run.ptr(hs[1]), run.ptr(pack_f16(run, keep, wp)), run.ptr(hs[2])
-    out = run.put(nan_like((n, h, wd, cout)))
-    st = run.put(nan_like((n, cout // 32, L.dmd_conv_stat_tiles(h, wd), 2), np.float64)) if want_stats else None
-    p.out, p.out_stats = run.ptr(out), run.ptr(st)
-    if expect is not None:
-        buf = (C.c_char * 96)()
-        check(run, L.dmd_conv2d_kernel_name(p, buf, 96), "dmd_conv2d_kernel_name")
-        assert buf.value.decode() == expect, buf.value
-    check(run, L.dmd_conv2d(p, run.stream()), "dmd_conv2d")
-    return run.get(out), (run.get(st) if want_stats else None)
-
-
 # ---- the bound -----------------------------------------------------------------------------------------------------------------------
-def rows_errors(got, truth):
-    """(B, M) tensors -> (B,): max |got - truth| of a row / max |truth| of the same row, non-finite entries left out; a row whose
-    truth is zero throughout has error 0 where got is zero throughout too, else infinity"""
-    fin = lambda x: torch.where(torch.isfinite(x), x.abs(), torch.zeros_like(x)).amax(dim=1)
-    d, s = fin(got.double() - truth.double()), fin(truth.double())
-    return torch.where(s > 0, d / s.clamp_min(1e-300), torch.where(d > 0, torch.full_like(d, math.inf), torch.zeros_like(d)))
-
-
 def image_blocks(x, block=32):
     """(N, ..., C) -> (N * C / block, M): one row per (image, `block`-channel block)"""
     n, c = x.shape[0], x.shape[-1]
@@ -651,21 +483,10 @@ def test_gn_silu_bwd(run, name, arm):
     """dx per (image, group), dmul / dadd per channel, against float64 autograd of silu(group_norm(x) * (1 + mul) + add); a zero
     image gives finite gradients; nothing is written outside the valid extent"""
     s = BWD_SITES[name]
-    L = run.lib()
     for shift in shifts_of(s["c"]):
         a, da, dskip, formula, truth, stick = bwd_case(name, arm, shift)
-        n, hw, c, keep = a.n, a.h * a.w, a.c, []
-        p = nv.GnBwdParams()
-        p.N, p.HW, p.C, p.identity_activation = n, hw, c, 0
-        if s.get("valid"):
-            p.W, p.valid_h, p.valid_w = a.w, a.hv, a.wv
-        hs = [run.put(t) for t in (a.x, da, dskip)]
-        outs = [run.put(nan_like(a.x.shape)), run.put(nan_like((n, c))), run.put(nan_like((n, c)))]
-        ws = run.put(np.zeros(int(L.dmd_gn_bwd_workspace_bytes(n, hw, c)), dtype=np.uint8))
-        p.x, p.norm, p.da, p.dskip = run.ptr(hs[0]), act_norm(run, keep, a), run.ptr(hs[1]), run.ptr(hs[2])
-        p.dx, p.workspace, p.dmul, p.dadd = run.ptr(outs[0]), run.ptr(ws), run.ptr(outs[1]), run.ptr(outs[2])
-        check(run, L.dmd_gn_silu_bwd(p, run.stream()), "dmd_gn_silu_bwd")
-        dx, dmul, dadd = (run.get(o) for o in outs)
+        c = a.c
+        dx, dmul, dadd = launch_gn_silu_bwd(run, a, da, dskip, valid=bool(s.get("valid")))
         if s.get("valid"):
             assert not dx[:, a.hv:].any() and not dx[:, :, a.wv:].any()
         dx = torch.from_numpy(np.ascontiguousarray(dx[:, :a.hv, :a.wv]))
@@ -715,39 +536,10 @@ def lowres_case(c, arm, shift):
 def test_lowres_chains(run, c, arm):
     """dmd_lowres_chain (three blocks: plain, attention, cat + projection + attention) and dmd_lowres_chain32 (two blocks) with the
     families at the chain input: the chains' own sums and their two private finish_stats"""
-    L = run.lib()
     for shift in shifts_of(c):
         a, blocks, formula, truth, stick = lowres_case(c, arm, shift)
-        n, keep = a.n, []
-        cols, table = [], []
-
-        def column(v):  # (N, m) -> its first column in the FiLM table
-            cols.append(sum(t.shape[1] for t in table))
-            table.append(v)
-            return cols[-1]
-
-        p = nv.LowresChainParams()
-        p.N, p.nblocks, p.input_save_slot = n, len(blocks), (0 if c == 64 else -1)
-        for i, b in enumerate(blocks):
-            cb = p.blocks[i]
-            cb.skip_slot, cb.save_slot, cb.has_attn = (1 if b["cat"] else -1), b["save"], int(b["attn"])
-            o_mul, o_add = column(b["f1"][0]), column(b["f1"][1])
-            cb.film1_mul[0], cb.film1_add[0], cb.film1_mul[1], cb.film1_add[1] = o_mul, o_add, o_mul + c, o_add + c
-            cb.film2_mul, cb.film2_add = column(b["f2"][0]), column(b["f2"][1])
-            hb = {key: run.put(b[key]) for key in ("b1", "b2", "bp", "gam", "bet", "bqkv", "bo") if key in b}
-            keep.append(hb)
-            cb.w1, cb.w2, cb.b1, cb.b2 = run.ptr(pack_f16(run, keep, b["w1"])), run.ptr(pack_f16(run, keep, b["w2"])), run.ptr(hb["b1"]), run.ptr(hb["b2"])
-            if b["cat"]:
-                cb.wproj, cb.bproj = run.ptr(pack_f16(run, keep, b["wp"])), run.ptr(hb["bp"])
-            if b["attn"]:
-                cb.wq, cb.wk, cb.wv = (run.ptr(pack_f16(run, keep, np.ascontiguousarray(b["wqkv"][j * c:(j + 1) * c]))) for j in range(3))
-                cb.wo = run.ptr(pack_f16(run, keep, b["wo"]))
-                cb.gn_gamma, cb.gn_beta, cb.bqkv, cb.bo = run.ptr(hb["gam"]), run.ptr(hb["bet"]), run.ptr(hb["bqkv"]), run.ptr(hb["bo"])
-        tab = np.ascontiguousarray(np.concatenate(table, axis=1))
-        hx, ht, out = run.put(a.x), run.put(tab), run.put(nan_like(a.x.shape))
-        p.x, p.out, p.table, p.table_stride = run.ptr(hx), run.ptr(out), run.ptr(ht), tab.shape[1]
-        check(run, (L.dmd_lowres_chain if c == 64 else L.dmd_lowres_chain32)(p, run.stream()), "dmd_lowres_chain")
-        bound = check_bound(run, f"chain{c}", arm, run.get(out), truth, stick, K_SPLIT, FLOOR_SPLIT, what=f" shift={shift}" if shift else "")
+        got = launch_lowres_chain(run, a.x, blocks)
+        bound = check_bound(run, f"chain{c}", arm, got, truth, stick, K_SPLIT, FLOOR_SPLIT, what=f" shift={shift}" if shift else "")
         nb = c // 32
         ids = [i * nb + j for i in sensitive_images(arm, c, shift) for j in range(nb)]
         check_sees_eps(lambda eps: formula(torch.float64, eps), truth, bound, image_blocks, ids)

@@ -988,17 +988,18 @@ def _ada_gn_silu(x, scale, shift):
 @pytest.mark.parametrize("schedule", SCHEDULES)
 @pytest.mark.parametrize("c", [64, 32], ids=["denoiser-64ch", "rew-end-32ch"])
 def test_lowres_chain(c, schedule, monkeypatch, request):
+    from tests import abi
+
     monkeypatch.setenv("SIMT_SCHEDULE", str(schedule))
     rng = np.random.default_rng(41 + c)
-    L = S.lib()
     n = 2
     x = rng.standard_normal((n, 8, 8, c)).astype(np.float32)
     table = (rng.standard_normal((n, 40 * c)) * 0.3).astype(np.float32)
     col = [0]
 
-    def take(k):
+    def take(k):  # the next k columns of the table
         col[0] += k
-        return col[0] - k
+        return table[:, col[0] - k:col[0]]
 
     def conv_w(co, ci, k):
         return (rng.standard_normal((co, ci, k, k)) / np.sqrt(ci * k * k)).astype(np.float32)
@@ -1008,42 +1009,20 @@ def test_lowres_chain(c, schedule, monkeypatch, request):
     specs = [dict(cat=False, attn=False, save=1 if c == 64 else -1), dict(cat=False, attn=True, save=-1)]
     if c == 64:
         specs.append(dict(cat=True, attn=True, save=-1))
-    p = nv.LowresChainParams()
-    p.N, p.nblocks, p.input_save_slot = n, len(specs), (0 if c == 64 else -1)
-    out = np.full_like(x, np.nan)
-    p.x, p.out, p.table, p.table_stride = S.ptr(x), S.ptr(out), S.ptr(table), table.shape[1]
-    keep, blocks = [], []
-    for i, sp in enumerate(specs):
+    blocks = []
+    for sp in specs:
         cin = 2 * c if sp["cat"] else c
         b = dict(sp, w1=conv_w(c, cin, 3), w2=conv_w(c, c, 3), b1=rng.standard_normal(c).astype(np.float32),
                  b2=rng.standard_normal(c).astype(np.float32))
-        cb = p.blocks[i]
-        cb.skip_slot, cb.save_slot = (1 if sp["cat"] else -1), sp["save"]
-        o1 = take(2 * cin)
-        cb.film1_mul[0], cb.film1_add[0] = o1, o1 + cin
-        cb.film1_mul[1], cb.film1_add[1] = o1 + c, o1 + cin + c
-        b["f1"] = (table[:, o1:o1 + cin], table[:, o1 + cin:o1 + 2 * cin])
-        o2 = take(2 * c)
-        cb.film2_mul, cb.film2_add = o2, o2 + c
-        b["f2"] = (table[:, o2:o2 + c], table[:, o2 + c:o2 + 2 * c])
-        packs = [_pack16(b["w1"]), _pack16(b["w2"])]
-        cb.w1, cb.w2, cb.b1, cb.b2 = S.ptr(packs[0]), S.ptr(packs[1]), S.ptr(b["b1"]), S.ptr(b["b2"])
+        b["f1"], b["f2"] = (take(cin), take(cin)), (take(c), take(c))
         if sp["cat"]:
             b["wp"], b["bp"] = conv_w(c, cin, 1), rng.standard_normal(c).astype(np.float32)
-            packs.append(_pack16(b["wp"]))
-            cb.wproj, cb.bproj = S.ptr(packs[-1]), S.ptr(b["bp"])
         if sp["attn"]:
-            cb.has_attn = 1
             b["wqkv"], b["bqkv"] = conv_w(3 * c, c, 1), (rng.standard_normal(3 * c) * 0.2).astype(np.float32)
             b["wo"], b["bo"] = conv_w(c, c, 1), rng.standard_normal(c).astype(np.float32)
             b["gam"], b["bet"] = (1 + 0.2 * rng.standard_normal(c)).astype(np.float32), (0.2 * rng.standard_normal(c)).astype(np.float32)
-            qkv = [_pack16(np.ascontiguousarray(b["wqkv"][k * c:(k + 1) * c])) for k in range(3)]
-            packs += qkv + [_pack16(b["wo"])]
-            cb.wq, cb.wk, cb.wv, cb.wo = (S.ptr(t) for t in packs[-4:])
-            cb.gn_gamma, cb.gn_beta, cb.bqkv, cb.bo = S.ptr(b["gam"]), S.ptr(b["bet"]), S.ptr(b["bqkv"]), S.ptr(b["bo"])
-        keep.append(packs)
         blocks.append(b)
-    S.check((L.dmd_lowres_chain if c == 64 else L.dmd_lowres_chain32)(p, None), "dmd_lowres_chain")
+    out = abi.launch_lowres_chain(abi.Simt, x, blocks, pack=lambda run, keep, w: keep.append(_pack16(w)) or keep[-1])  # dmd_pack_jobs
     _same_bits_as_schedule_0(request, schedule, out)
 
     # fp64 restatement of ResBlock.forward (blocks.py:141-147) / SelfAttention2d.forward (blocks.py:62-72)

@@ -28,7 +28,6 @@ Bounds
 
 What the interpreter cannot reproduce: the order of the sums inside an MFMA is its own, so the split rows differ between the
 runners by small factors (profiles/wgrad_precision.txt has both)."""
-import ctypes as C
 import functools
 import math
 
@@ -36,11 +35,11 @@ import numpy as np
 import pytest
 import torch
 
-from diamond_amd import native as nv  # struct layouts and the signature table only
+from diamond_amd import native as nv  # struct layouts only
 from tests import groupnorm_cases as GC
 from tests import wgrad_cases as WC
-from tests.test_groupnorm_precision import (FLOOR_EXACT, K_BWD, RUNNERS, Gpu, Simt, check, kernel_sums, nan_like, norm_struct,  # noqa: F401
-                                            rows_errors)
+from tests.abi import RUNNERS, check, kernel_sums, launch_wgrad, nan_like, norm_struct
+from tests.groupnorm_cases import FLOOR_EXACT, K_BWD, rows_errors
 
 SITES = [(2, 1, 9), (4, 1, 9), (1, 4, 9), (2, 2, 9), (4, 2, 9), (4, 4, 9), (4, 2, 1), (2, 2, 1), (4, 4, 1)]
 SITE_IDS = ["%d-%d-%d" % s for s in SITES]
@@ -52,34 +51,6 @@ SHAPES = [(3, 8, 8), (3, 8, 16)]  # 3 sub-tiles (the last tile half empty, its f
 def T(a):
     """a tensor copy of a (possibly read-only) array"""
     return torch.tensor(np.asarray(a))
-
-
-def launch_wgrad(run, c, cout, taps, precision, prologue=0, norm=None, defer_into=None):
-    """dmd_conv2d_wgrad on a wgrad_cases.Case -> (dw, db); defer_into = (job, dw handle, db handle or None): defer_reduce = 1, the
-    job filled by dmd_wgrad_job, its partials kept alive by the returned handle"""
-    L, keep = run.lib(), []
-    n, h, w, cin = c.x.shape
-    p = nv.WgradParams()
-    p.N, p.H, p.W, p.Cout, p.taps, p.cin_real, p.precision = n, h, w, cout, taps, c.cin_real, precision
-    if c.valid is not None:
-        p.valid_h, p.valid_w = c.valid
-    hx, hdy = run.put(c.x), run.put(c.dy)
-    p.src.x, p.src.C, p.src.prologue, p.dy = run.ptr(hx), cin, prologue, run.ptr(hdy)
-    if prologue:
-        p.src.norm = norm(run, keep)
-    if defer_into is not None:
-        job, hdw, hdb = defer_into
-        p.dw, p.dbias, p.defer_reduce = run.ptr(hdw), run.ptr(hdb), 1
-        check(run, L.dmd_wgrad_job(p, job), "dmd_wgrad_job")
-        ws = run.put(nan_like(job.num_wg * (job.NB * job.NCO * 256 + job.NCO * 16)))
-        p.workspace = job.partials = run.ptr(ws)
-        check(run, L.dmd_conv2d_wgrad(p, run.stream()), "dmd_conv2d_wgrad")
-        return ws, (hx, hdy, keep)
-    hdw, hdb = run.put(nan_like((cout, c.cin_real, c.k, c.k))), run.put(nan_like(cout))
-    ws = run.put(nan_like(int(L.dmd_wgrad_workspace_floats(p))))
-    p.workspace, p.dw, p.dbias = run.ptr(ws), run.ptr(hdw), run.ptr(hdb)
-    check(run, L.dmd_conv2d_wgrad(p, run.stream()), "dmd_conv2d_wgrad")
-    return run.get(hdw), run.get(hdb)
 
 
 def check_case(run, tag, c, nci, dw, db, route, plain_rows=None):

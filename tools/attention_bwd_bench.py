@@ -88,6 +88,7 @@ def timing(args):
 
 def precision(args):
     from tests import test_attention_bwd_mfma as M
+    from tests import attention_cases as A
     from tests import test_attention_precision as P
 
     lines = [f"dmd_attention_bwd_mfma against dmd_attention_bwd on the same inputs, {box()}",
@@ -97,10 +98,10 @@ def precision(args):
              f"{'family':>7} {'a':>4} {'T':>5} {'y':>8} | {'mfma dq':>8} {'dk':>7} {'dv':>7} | {'scalar dq':>9} {'dk':>7} {'dv':>7} | mfma > scalar"]
     worst = (0.0, "")
     for t in (64, 256, 1024):
-        for family, a in P.BWD_CASES:
+        for family, a in A.BWD_CASES:
             for y_from in ("forward", "truth"):
                 e, e32 = M.measure(M.GPU, t, family, a, y_from)
-                s, _ = M.measure(M.GPU, t, family, a, y_from, run=P.Gpu.attention_bwd)
+                s, _ = M.measure(M.GPU, t, family, a, y_from, run=P.GPU.attention_bwd)
                 rm, rs = (e / e32).amax(dim=(0, 2)), (s / e32).amax(dim=(0, 2))
                 over = [n for n, x, z in zip(("dq", "dk", "dv"), rm, rs) if float(x) > float(z)]
                 lines.append(f"{family:>7} {a:>4} {t:>5} {y_from:>8} | {float(rm[0]):8.2f} {float(rm[1]):7.2f} {float(rm[2]):7.2f} | "

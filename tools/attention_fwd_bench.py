@@ -244,7 +244,7 @@ handling enters (one key, one query; on the interpreter at C = 16, whose smalles
 
 def precision_f16x2(args):
     from tests import test_attention_f16x2_extent as X
-    from tests import test_attention_precision as P
+    from tests import attention_cases as P
 
     arm = X.GPU
     lines = [f"dmd_attention_f16x2 (attention_f16x2_kernel over a valid extent), {box()}",
@@ -271,7 +271,7 @@ def precision_f16x2(args):
 
 def precision(args):
     from tests import test_attention_f32_tiled as F
-    from tests import test_attention_precision as P
+    from tests import attention_cases as P
 
     lines = [f"dmd_attention_f32 (attention_f32_tiled_kernel) beside attention_kernel on the same inputs, {box()}",
              f"N = {F.N}; error per (image, head) against float64 as a ratio to max(float32 CPU evaluation's error, 2^-24); largest ratio over",
@@ -282,15 +282,15 @@ def precision(args):
         for label, ref in list(F.precision_cases(t, c)) + ([("6a k, v = 1e5", F.beyond_fp16_case(t, c)[0])] if t == 256 else []):
             e, r = F.ratios(ref, F.GPU.attention(ref.qkv, c))
             i = int(r.argmax())
-            other = f"{float(F.ratios(ref, P.Gpu.attention(ref.qkv, c, exact=True))[1].max()):22.2f}" if t % 64 == 0 else f"{'-':>22}"
+            other = f"{float(F.ratios(ref, F.GPU.other(ref.qkv, c, exact=True))[1].max()):22.2f}" if t % 64 == 0 else f"{'-':>22}"
             lines.append(f"{label:>20} {t:>5} {c:>3} | {float(e.flatten()[i]):10.3e} {float(ref.e32.flatten()[i]):10.3e} {float(r.max()):6.2f} | {other}")
             if float(r.max()) > worst[0]:
                 worst = (float(r.max()), f"family {label}, T = {t}, C = {c}")
-    for h, w, vh, vw in F.V.CASES:
+    for h, w, vh, vw in P.EXTENT_CASES:
         qkv, ref, _ = F.extent_inputs(h, w, vh, vw)
-        e, r = F.ratios(ref, F.GPU.run(qkv, h, w, vh, vw, F.V.C)[:, :vh, :vw].reshape(F.V.N, vh * vw, F.V.C))
+        e, r = F.ratios(ref, F.GPU.run(qkv, h, w, vh, vw, P.EXTENT_C)[:, :vh, :vw].reshape(P.EXTENT_N, vh * vw, P.EXTENT_C))
         i = int(r.argmax())
-        lines.append(f"{f'extent {h}x{w}/{vh}x{vw}':>20} {vh * vw:>5} {F.V.C:>3} | {float(e.flatten()[i]):10.3e} {float(ref.e32.flatten()[i]):10.3e} "
+        lines.append(f"{f'extent {h}x{w}/{vh}x{vw}':>20} {vh * vw:>5} {P.EXTENT_C:>3} | {float(e.flatten()[i]):10.3e} {float(ref.e32.flatten()[i]):10.3e} "
                      f"{float(r.max()):6.2f} | {'-':>22}")
         if float(r.max()) > worst[0]:
             worst = (float(r.max()), f"extent {h}x{w}/{vh}x{vw}")
