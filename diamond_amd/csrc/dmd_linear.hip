@@ -171,7 +171,9 @@ extern "C" int dmd_linear(const dmd_linear_params* p, dmd_stream_t stream) {
   DMD_CHECK_ARG(p->M > 0 && p->N > 0 && p->K > 0, "linear: bad M/N/K %d %d %d", p->M, p->N, p->K);
   DMD_CHECK_ARG((p->trans_a | p->trans_w | 1) == 1, "linear: trans_a / trans_w are 0 or 1");
   // the either-storage-order instance wherever the 16-byte loads cannot run: a transposed operand, a K tail, unaligned rows
-  const bool trans = p->trans_a || p->trans_w || p->K % 16 != 0 || p->lda % 4 != 0 || p->ldw % 4 != 0;
+  // (a row stride that is no multiple of 4 floats, or an operand that does not begin on a 16-byte boundary)
+  const bool trans = p->trans_a || p->trans_w || p->K % 16 != 0 || p->lda % 4 != 0 || p->ldw % 4 != 0 ||
+                     (uintptr_t)p->A % 16 != 0 || (uintptr_t)p->W % 16 != 0;
   // the choice depends on K alone -- not on M (the batch), the data or the device: an output row is summed in the same
   // order whatever the batch size it is computed in.  With a masked tail it is K rounded up to 16: the route of the call on
   // the zero-padded copy.

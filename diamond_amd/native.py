@@ -439,7 +439,8 @@ def linear(a: Tensor, w: Tensor, bias: Optional[Tensor], out: Tensor, accumulate
     p.C, p.ldc = ptr(out), out.stride(0)
     p.accumulate, p.silu = int(accumulate), int(silu)
     if PROFILER is not None:
-        PROFILER.annotate(f"linear_mfma_kernel<{'true' if (p.K + 15) // 16 * 16 >= 512 else 'false'}>", 2.0 * p.M * p.N * p.K,
+        kp = (p.K + 15) // 16 * 16  # dmd_linear's split-K rule (csrc/dmd_linear.hip)
+        PROFILER.annotate(f"linear_mfma_kernel<{'true' if kp >= 512 and kp % 64 == 0 else 'false'}>", 2.0 * p.M * p.N * p.K,
                           4.0 * (p.M * p.K + p.N * p.K + p.M * p.N))
     check(lib().dmd_linear(C.byref(p), stream()), "dmd_linear")
     return out

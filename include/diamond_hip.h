@@ -194,9 +194,13 @@ typedef struct dmd_linear_params {
   int32_t silu;       /* 1: C = silu(...) */
   /* Operands in either storage order (the backward's data / weight gradient GEMMs): trans_a = 1: A is given as (K, M) row-major,
    * lda = the stride between its K rows; trans_w = 1: W is given as (K, N) row-major likewise.  The instance that reads them also
-   * runs K-contiguous operands whose K is no multiple of 16 (the tail is masked: exact zeros) or whose lda / ldw is no multiple
-   * of 4.  The result is BITWISE the plain call on K-contiguous copies zero-padded to K rounded up to 16: same 16-wide
-   * steps, same four MFMAs per step, and the split-K route is chosen by the rounded K. */
+   * runs K-contiguous operands whose K is no multiple of 16 (the tail is masked: exact zeros), whose lda / ldw is no multiple
+   * of 4, or whose A / W pointer is not 16-byte aligned (any 4-byte-aligned pointer is a legal operand: the host looks at the
+   * pointers, the 16-byte loads are never issued on a misaligned row).  The result is BITWISE the plain call on aligned
+   * K-contiguous copies zero-padded to K rounded up to 16: same 16-wide steps, same four MFMAs per step, and the split-K route
+   * is chosen by the rounded K: Kp >= 512 and Kp % 64 == 0 split (four K quarters, summed ((w0 + w1) + w2) + w3); every other K
+   * -- 496, 528, 608, 1008 among them -- is ONE chain of Kp and on the interpreter about 2x less accurate than K = 512
+   * (profiles/linear_precision.txt).  A weight gradient whose K = (T - 1) * B falls there; moving the rule changes bits. */
   int32_t trans_a, trans_w;
 } dmd_linear_params;
 int dmd_linear(const dmd_linear_params* p, dmd_stream_t stream);

@@ -378,3 +378,71 @@ def launch_lowres_chain(run, x, blocks, pack=pack_f16):
     p.x, p.out, p.table, p.table_stride = run.ptr(hx), run.ptr(out), run.ptr(ht), tab.shape[1]
     check(run, (run.lib().dmd_lowres_chain if c == 64 else run.lib().dmd_lowres_chain32)(p, run.stream()), "dmd_lowres_chain")
     return run.get(out)
+
+
+# ---- dmd_linear ----------------------------------------------------------------------------------------------------------------------
+def _aligned(run, storage, offset):
+    """(handle, address of storage[0]): a flat copy of `storage` behind `offset` floats of NaN in a buffer that begins on a 16-byte
+    boundary (its length rounded up to 4 floats, NaN as well, so that both runners place it so: at most 3 floats of slack before
+    the interpreter's fence)"""
+    flat = storage.reshape(-1)
+    buf = nan_like(-(-(offset + flat.size) // 4) * 4)
+    buf[offset:offset + flat.size] = flat
+    h = run.put(buf)
+    assert run.ptr(h) % 16 == 0
+    return h, run.ptr(h) + 4 * offset
+
+
+def linear(run, a, w, bias=None, c0=None, silu=False, trans_a=False, trans_w=False, pad=(0, 0, 0), offset=(0, 0), status=False):
+    """dmd_linear on the LOGICAL operands a (M, K), w (N, K) -> (C (M, N), the storage of C (M, N + pad[2])).  An operand is laid
+    out K-contiguous as (rows, K + pad) or, transposed, as (K, rows + pad) -- with a pad also one more row beyond K --, the pad
+    floats of lda / ldw / ldc NaN: no instance may read them.  offset = (floats of A, of W) past a 16-byte boundary at which the
+    operand's first element sits.  c0 (M, N): C starts as it and the call accumulates; otherwise C starts as NaN."""
+    a, w = np.asarray(_array(a), dtype=np.float32), np.asarray(_array(w), dtype=np.float32)
+    (m, k), n = a.shape, w.shape[0]
+    assert w.shape[1] == k
+
+    def lay(x, trans, extra):
+        st = nan_like((k + (extra > 0), x.shape[0] + extra) if trans else (x.shape[0], k + extra))
+        if trans:
+            st[:k, :x.shape[0]] = x.T
+        else:
+            st[:, :k] = x
+        return st, st.shape[1]
+
+    (sa, lda), (sw, ldw) = lay(a, trans_a, pad[0]), lay(w, trans_w, pad[1])
+    (ha, pa), (hw, pw) = _aligned(run, sa, offset[0]), _aligned(run, sw, offset[1])
+    sc = nan_like((m, n + pad[2]))
+    if c0 is not None:
+        sc[:, :n] = _array(c0)
+    hb, hc = run.put(None if bias is None else np.asarray(_array(bias), dtype=np.float32)), run.put(sc)
+    p = nv.LinearParams()
+    p.M, p.N, p.K, p.A, p.lda, p.W, p.ldw, p.bias, p.C, p.ldc = m, n, k, pa, lda, pw, ldw, run.ptr(hb), run.ptr(hc), n + pad[2]
+    p.accumulate, p.silu, p.trans_a, p.trans_w = int(c0 is not None), int(silu), int(trans_a), int(trans_w)
+    rc = run.lib().dmd_linear(C.byref(p), run.stream())
+
+    def outs(keep=(ha, hw, hb)):  # (the operands stay alive until the result is back)
+        st = run.get(hc)
+        return np.ascontiguousarray(st[:, :n]), st
+
+    return _finish(run, rc, "dmd_linear", status, outs)
+
+
+# ---- dmd_lstm_pointwise / dmd_lstm_pointwise_bwd -------------------------------------------------------------------------------------
+def lstm_pointwise(run, gates, c_prev):
+    """gates (N, 4 Hd) in i, f, g, o order, c_prev (N, Hd) -> (h, c)"""
+    n, hd = c_prev.shape
+    hg, hc = run.put(np.asarray(_array(gates), dtype=np.float32)), run.put(np.asarray(_array(c_prev), dtype=np.float32))
+    h, c = run.put(nan_like((n, hd))), run.put(nan_like((n, hd)))
+    check(run, run.lib().dmd_lstm_pointwise(run.ptr(hg), run.ptr(hc), run.ptr(h), run.ptr(c), n, hd, run.stream()), "dmd_lstm_pointwise")
+    return run.get(h), run.get(c)
+
+
+def lstm_pointwise_bwd(run, gates, c_prev, c_new, dh, dc):
+    """-> (dgates (N, 4 Hd), dc_prev (N, Hd)); dh / dc may be None (the kernel's NULL: a zero gradient)"""
+    n, hd = c_prev.shape
+    hs = [run.put(None if x is None else np.asarray(_array(x), dtype=np.float32)) for x in (gates, c_prev, c_new, dh, dc)]
+    dg, dcp = run.put(nan_like((n, 4 * hd))), run.put(nan_like((n, hd)))
+    check(run, run.lib().dmd_lstm_pointwise_bwd(*(run.ptr(x) for x in hs), run.ptr(dg), run.ptr(dcp), n, hd, run.stream()),
+          "dmd_lstm_pointwise_bwd")
+    return run.get(dg), run.get(dcp)
