@@ -1047,6 +1047,156 @@ extern "C" int dmd_segment_gather(const dmd_segment_gather_params* pp, dmd_strea
   return 0;
 }
 
+// ---- device-resident replay store: a window of env steps INTO the uint8 arena in one launch -------------------------------------
+// (reference coroutines/collector.py:53-106: a host Episode concatenated step by step, the grown episode uploaded whole again.)
+// HBM-bound the other way round: 4 bytes read and 1 written per value.  grid.x runs over FRAMES -- the launch's `total` frames in
+// run order, then one workgroup per 256 frames for their small fields --, grid.y over a frame's chunks of 256 x W levels, so a
+// workgroup's run (kind, source row, destination row) is uniform: the (R, 4) table is walked through scalar loads (R is a window's
+// envs + deaths + moved episodes: tens) and no lane diverges.  W as in the gather: 16 = four words per lane 256 words apart, every
+// 16-byte fp32 load of a wave 1 KiB contiguous, every 4-byte packed store 256 bytes contiguous, four loads in flight; 4 = one word
+// per lane; 1 = one level per lane, any per_frame, any alignment.  A kind-2 run (an episode moving to a larger slot) copies words.
+__device__ __forceinline__ uint32_t rec_levels4(f32x4 v, bool& bad) {
+  uint32_t pk = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float lc = dmd_level(v[e]);
+    bad |= !((lc / 255.0f) * 2.0f - 1.0f == v[e]);  // quantize_u8_kernel's rule
+    pk |= (uint32_t)lc << (8 * e);
+  }
+  return pk;
+}
+
+// the run that holds frame f of the launch: (kind, source row, destination row) of that frame; false for a frame beyond the
+// runs' sum or in a run the contract excludes (n < 1 is never entered; unknown kind, rows outside the arrays)
+__device__ __forceinline__ bool rec_locate(const dmd_record_window_params& p, int64_t f, int64_t& kind, int64_t& src, int64_t& dst) {
+  int64_t at = 0;
+  for (int r = 0; r < p.R; ++r) {
+    const int64_t n = p.runs[r * 4 + 2];
+    if (n < 1) continue;
+    if (f < at + n) {
+      kind = p.runs[r * 4 + 0];
+      const int64_t s0 = p.runs[r * 4 + 1], d0 = p.runs[r * 4 + 3];
+      src = s0 + (f - at);
+      dst = d0 + (f - at);
+      if (s0 < 0 || d0 < 0) return false;
+      if (kind == 0) return s0 + n <= p.steps && d0 + n <= p.F;
+      if (kind == 1) return p.final_obs && p.finals && n == 1 && s0 < p.K && d0 < p.E;
+      if (kind == 2) return s0 + n <= p.F && d0 + n <= p.F;
+      return false;
+    }
+    at += n;
+  }
+  return false;
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void record_window_kernel(dmd_record_window_params p, int64_t units) {
+  int64_t kind = 0, src = 0, dst = 0;
+  if ((int64_t)blockIdx.x >= p.total) {  // the small fields of 256 frames, one lane each
+    if (blockIdx.y != 0) return;
+    const int64_t f = ((int64_t)blockIdx.x - p.total) * 256 + threadIdx.x;
+    if (f >= p.total || !rec_locate(p, f, kind, src, dst) || kind == 1) return;
+    if (kind == 0) {
+      p.arena_act[dst] = p.act[src];
+      p.arena_rew[dst] = p.rew[src];
+      if (p.flag_size == 8) {
+        p.arena_end[dst] = ((const int64_t*)p.end)[src] != 0;
+        p.arena_trunc[dst] = ((const int64_t*)p.trunc)[src] != 0;
+      } else {
+        p.arena_end[dst] = ((const uint8_t*)p.end)[src] != 0;
+        p.arena_trunc[dst] = ((const uint8_t*)p.trunc)[src] != 0;
+      }
+    } else {
+      p.arena_act[dst] = p.arena_act[src];
+      p.arena_rew[dst] = p.arena_rew[src];
+      p.arena_end[dst] = p.arena_end[src];
+      p.arena_trunc[dst] = p.arena_trunc[src];
+    }
+    return;
+  }
+  if (!rec_locate(p, blockIdx.x, kind, src, dst)) return;
+  const float* sf = kind == 0 ? p.obs + src * p.per_frame : (kind == 1 ? p.final_obs + src * p.per_frame : nullptr);
+  const uint8_t* sb = p.frames + src * p.per_frame;  // (followed for kind 2 only)
+  uint8_t* out = (kind == 1 ? p.finals : p.frames) + dst * p.per_frame;
+  const int64_t chunk = blockIdx.y;  // 256 lanes x W levels
+  bool bad = false;
+  if (W == 16) {
+    const int64_t words = units * 4;  // the chunk's words: chunk * 1024 ... + 1023
+    if (sf) {
+      f32x4 v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t w = chunk * 1024 + j * 256 + threadIdx.x;
+        if (w < words) v[j] = *(const f32x4*)(sf + w * 4);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t w = chunk * 1024 + j * 256 + threadIdx.x;
+        if (w < words) *(uint32_t*)(out + w * 4) = rec_levels4(v[j], bad);
+      }
+    } else {
+      uint32_t pk[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t w = chunk * 1024 + j * 256 + threadIdx.x;
+        if (w < words) pk[j] = *(const uint32_t*)(sb + w * 4);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t w = chunk * 1024 + j * 256 + threadIdx.x;
+        if (w < words) *(uint32_t*)(out + w * 4) = pk[j];
+      }
+    }
+  } else {
+    const int64_t u = chunk * 256 + threadIdx.x;  // this lane's unit of W levels
+    if (u < units) {
+      if (W == 4) {
+        *(uint32_t*)(out + u * 4) = sf ? rec_levels4(*(const f32x4*)(sf + u * 4), bad) : *(const uint32_t*)(sb + u * 4);
+      } else if (sf) {
+        const float v = sf[u], lc = dmd_level(v);
+        bad = !((lc / 255.0f) * 2.0f - 1.0f == v);
+        out[u] = (uint8_t)lc;
+      } else {
+        out[u] = sb[u];
+      }
+    }
+  }
+  if (bad) *p.off_grid = 1;  // benign race: every writer stores 1
+}
+
+extern "C" int dmd_record_window(const dmd_record_window_params* pp, dmd_stream_t stream) {
+  DMD_CHECK_ARG(pp, "record_window: null parameter block");
+  const dmd_record_window_params& p = *pp;
+  DMD_CHECK_ARG(p.R >= 0 && p.total >= 0 && p.steps >= 0 && p.K >= 0 && p.F >= 0 && p.E >= 0 && p.per_frame >= 1,
+                "record_window: R %d, total %lld, steps %lld, K %lld, F %lld, E %lld, per_frame %lld", p.R, (long long)p.total,
+                (long long)p.steps, (long long)p.K, (long long)p.F, (long long)p.E, (long long)p.per_frame);
+  DMD_CHECK_ARG(p.flag_size == 1 || p.flag_size == 8, "record_window: end / trunc elements of %d bytes (1 or 8)", p.flag_size);
+  if (p.R == 0 || p.total == 0) return 0;
+  DMD_CHECK_ARG(p.obs && p.act && p.rew && p.end && p.trunc, "record_window: null source array");
+  DMD_CHECK_ARG(p.frames && p.arena_act && p.arena_rew && p.arena_end && p.arena_trunc, "record_window: null arena array");
+  DMD_CHECK_ARG(p.runs && p.off_grid, "record_window: null runs or off_grid");
+  DMD_CHECK_ARG(p.K == 0 || (p.final_obs && p.finals), "record_window: K %lld final observations (kind 1) without final_obs or finals",
+                (long long)p.K);
+  const uintptr_t u8_bases = (uintptr_t)p.frames | (uintptr_t)p.finals;
+  const uintptr_t f32_bases = (uintptr_t)p.obs | (uintptr_t)p.final_obs;
+  const bool words = p.per_frame % 4 == 0 && u8_bases % 4 == 0 && f32_bases % 16 == 0;  // 16-byte loads, 4-byte stores
+  const int W = !words ? 1 : (p.per_frame % 16 == 0 ? 16 : 4);
+  const int64_t units = p.per_frame / W;
+  const int64_t bpf = (units + 255) / 256;
+  const int64_t gx = p.total + (p.total + 255) / 256;
+  DMD_CHECK_ARG(gx <= 0x7fffffffLL && bpf <= 65535 && gx * bpf <= 0x7fffffffLL,
+                "record_window: %lld frames of %lld workgroups: beyond one launch's grid", (long long)p.total, (long long)bpf);
+  const dim3 grid((unsigned)gx, (unsigned)bpf), block(256);
+  if (W == 16)
+    hipLaunchKernelGGL(record_window_kernel<16>, grid, block, 0, (hipStream_t)stream, p, units);
+  else if (W == 4)
+    hipLaunchKernelGGL(record_window_kernel<4>, grid, block, 0, (hipStream_t)stream, p, units);
+  else
+    hipLaunchKernelGGL(record_window_kernel<1>, grid, block, 0, (hipStream_t)stream, p, units);
+  DMD_LAUNCH_CHECK();
+  return 0;
+}
+
 // ---- open-loop world-model evaluation: one step closed on the device ------------------------------------------------------------
 // The sampler's frame `pred` against what the arena recorded at that episode step, then the ring advance from the prediction
 // (free running) or from the recording (teacher forced): the frame metrics in uint8 levels, the recorded reward / end of the

@@ -144,13 +144,16 @@ def _slots_env_loop(env, model, expo_fn: Optional[Callable[[Tensor], Tensor]], n
 
 
 @coroutine
-def make_env_loop(env, model, epsilon: float = 0.0, expo_fn: Optional[Callable[[Tensor], Tensor]] = None):
+def make_env_loop(env, model, epsilon: float = 0.0, expo_fn: Optional[Callable[[Tensor], Tensor]] = None, kind: Optional[str] = None):
     """Reference coroutines/env_loop.py:12-74.  For an env that resolves a step's deaths on the device (WorldModelEnv) and a policy
     with a separable encoder (ActorCritic), epsilon = 0: _slots_env_loop above -- DIAMOND_ENV_LOOP=sequential selects the loop
     below for them too (A/B, tests).  Anything else (the real envs of the collector, epsilon-greedy, other policies): the
-    reference's order of calls, one `env.step` and one host look at `dead` per step."""
+    reference's order of calls, one `env.step` and one host look at `dead` per step.
+    kind: "slots" | "sequential" for THIS loop, whatever DIAMOND_ENV_LOOP says (the collector records `final_observation`s, which
+    only the sequential loop's infos carry); None: the environment variable decides."""
     num_steps = yield
-    kind = os.environ.get("DIAMOND_ENV_LOOP", "slots")
+    if kind is None:
+        kind = os.environ.get("DIAMOND_ENV_LOOP", "slots")
     assert kind in ("slots", "sequential"), f"DIAMOND_ENV_LOOP={kind!r}: slots | sequential"
     separable = all(hasattr(model, a) for a in ("encode", "predict_from_features", "burn_in_from_features"))
     dev = model.device

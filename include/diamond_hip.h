@@ -481,6 +481,58 @@ typedef struct dmd_segment_gather_params {
 } dmd_segment_gather_params;
 int dmd_segment_gather(const dmd_segment_gather_params* p, dmd_stream_t stream);
 
+/* ---- device-resident replay store: a window of env steps written INTO the arena in ONE launch ----------------------------------
+ * (additive to ABI v11.)  Replaces the reference collector's path for collected steps (coroutines/collector.py:53-106: a host
+ * Episode concatenated per step, the whole grown episode handed over again) -- the frames are on the device when the env loop
+ * yields them.
+ * Sources (device): obs (steps, per_frame) fp32 in [-1, 1], act (steps) int64, rew (steps) fp32, end / trunc (steps) integers of
+ * flag_size bytes (1 or 8) -- the env loop's stacked (B, T, ...) tensors, steps = B * T, flattened index b * T + t -- and
+ * final_obs (K, per_frame) fp32 (NULL with K == 0).  Destinations: the arena arrays of dmd_segment_gather, F rows, and finals, E rows.
+ * runs (R, 4) int64 on the device, per run (kind, src, n, dst):
+ *   kind 0   the n consecutive source steps src ... src + n - 1 (one env's: src = b * T + t0) -> arena rows dst ... dst + n - 1, all
+ *            five fields: frames as levels, act and rew copied, end / trunc stored as (value != 0)
+ *   kind 1   final_obs[src] -> finals[dst], as levels (n = 1)
+ *   kind 2   arena rows src ... src + n - 1 -> arena rows dst ... dst + n - 1, all five fields, byte for byte (an episode that has
+ *            outgrown its slot moves)
+ * A level is clamp(rint((v + 1) / 2 * 255), 0, 255), dmd_quantize_u8's expression; *off_grid (int32, zeroed by the caller) becomes 1
+ * when some value is not bitwise (level / 255) * 2 - 1, that kernel's rule, and is not written otherwise.
+ * The caller guarantees: total == the sum of the runs' n; the source and destination rows of a kind-2 run do not overlap; no
+ * destination row of the launch is another run's source or destination.  The entry checks what it can see on the host (below);
+ * on the device a run with n < 1, an unknown kind, or rows outside steps / K / F / E is skipped whole: nothing outside the arrays
+ * is read or written.
+ * One workgroup per 256 x W levels of ONE frame (what it copies is uniform over it; the runs are read through scalar loads), the
+ * five small fields in workgroups of their own: the launched work is proportional to `total`.  W = 16 where per_frame % 16 == 0
+ * (four 16-byte fp32 loads 4 KiB apart in flight per lane, 4-byte packed stores), W = 4 where per_frame % 4 == 0 -- both need obs /
+ * final_obs 16-byte and frames / finals 4-byte aligned --, one level per lane otherwise: any per_frame >= 1, any alignment.
+ * R == 0 or total == 0 launches nothing and returns 0.  Refused (non-zero, dmd_last_error): a NULL array, runs or off_grid;
+ * flag_size other than 1 or 8; K > 0 without final_obs or finals; negative R, total, steps, K, F or E; per_frame < 1; a grid
+ * beyond one launch. */
+typedef struct dmd_record_window_params {
+  int32_t R;               /* runs */
+  int32_t flag_size;       /* bytes per element of the source end / trunc: 1 or 8 */
+  int64_t per_frame;       /* C * H * W */
+  int64_t total;           /* sum of the runs' n: the frames this launch writes */
+  int64_t steps;           /* B * T: rows of obs / act / rew / end / trunc */
+  int64_t K;               /* rows of final_obs */
+  int64_t F;               /* rows of the arena */
+  int64_t E;               /* rows of finals */
+  const float* obs;        /* (steps, per_frame) */
+  const int64_t* act;      /* (steps) */
+  const float* rew;        /* (steps) */
+  const void* end;         /* (steps) of flag_size bytes */
+  const void* trunc;       /* (steps) of flag_size bytes */
+  const float* final_obs;  /* (K, per_frame) or NULL */
+  uint8_t* frames;         /* (F, per_frame) */
+  int64_t* arena_act;      /* (F) */
+  float* arena_rew;        /* (F) */
+  uint8_t* arena_end;      /* (F) */
+  uint8_t* arena_trunc;    /* (F) */
+  uint8_t* finals;         /* (E, per_frame) or NULL */
+  const int64_t* runs;     /* (R, 4): kind, src, n, dst */
+  int32_t* off_grid;
+} dmd_record_window_params;
+int dmd_record_window(const dmd_record_window_params* p, dmd_stream_t stream);
+
 /* ---- open-loop world-model evaluation against the replay arena: one step closed on the device in ONE launch ------------------
  * (additive to ABI v11.)  The sampler has produced `pred` from the context rings; this call compares it with what the arena
  * recorded and advances the rings, from the prediction (free running) or from the recording (teacher forced).
