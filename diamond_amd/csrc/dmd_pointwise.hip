@@ -1350,6 +1350,134 @@ extern "C" int dmd_openloop_step(const dmd_openloop_params* pp, dmd_stream_t str
   return 0;
 }
 
+// ---- open-loop evaluation: what moved, and what copying a frame would have scored ------------------------------------------------
+// Launched BEFORE openloop_step_kernel of the same step, on the ring as it stands: the target y against the previous recorded
+// frame r and the context's last frame a (the two "models" that copy a frame), and the prediction's level q against the level m
+// of the ring's newest frame (what the model itself saw last) -- eight exact integer sums per sample, the contract at
+// dmd_openloop_motion in include/diamond_hip.h.  Read-only but for `out` / `out_valid`.  One workgroup per sample and the lane
+// walk of openloop_step_kernel (4-byte level words, 16-byte fp32 accesses, W = 16 / 4 / 1), per value 3 bytes of levels and 8 of
+// fp32 in; r and a are not loaded where they are not valid (level 0 stands in, the sums that use it are zeroed by lane 0), and a
+// sample without a target loads nothing at all.  Seven 64-bit sums: wave butterflies, then the four waves through LDS in order.
+#define OM_SUMS 7
+struct om_sums {
+  unsigned long long e[OM_SUMS];
+};
+
+// the target of sample b at `step`, nullptr where there is none: the rule of openloop_step_kernel, restated (that kernel's and
+// frame_ssim_tile_kernel's machine code stay as measured; the tests hold the three against each other on every kind of row)
+__device__ __forceinline__ const uint8_t* om_target(const dmd_openloop_motion_params& p, int64_t first, int64_t s, int64_t len,
+                                                    int64_t final_row, int64_t pf) {
+  if (s >= 0 && s < len) return p.frames + (first + s) * pf;
+  if (s == len && len >= 1 && final_row >= 0 && p.end[first + len - 1] != 0) return p.finals + final_row * pf;
+  return nullptr;
+}
+
+__device__ __forceinline__ void om_level(uint32_t y, uint32_t r, uint32_t a, float pv, float mv, om_sums& s) {
+  const int q = (int)dmd_level(pv), m = (int)dmd_level(mv);
+  const int dr = (int)y - (int)r, da = (int)y - (int)a, dq = q - (int)y;
+  const bool moved = dr != 0, pred_moved = q != m;
+  s.e[0] += (unsigned int)(dr * dr);
+  s.e[1] += (unsigned int)(da * da);
+  s.e[2] += moved ? 1u : 0u;
+  s.e[3] += pred_moved ? 1u : 0u;
+  s.e[4] += moved && pred_moved ? 1u : 0u;
+  s.e[5] += moved ? (unsigned int)(dq * dq) : 0u;
+  s.e[6] += moved && dq == 0 ? 1u : 0u;
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void openloop_motion_kernel(dmd_openloop_motion_params p) {
+  __shared__ unsigned long long red[4][OM_SUMS];
+  const int64_t b = blockIdx.x, pf = p.per_frame;
+  const int tid = threadIdx.x;
+  const int64_t first = p.seg[b * 4 + 0], start = p.seg[b * 4 + 1], len = p.seg[b * 4 + 2];
+  const int64_t final_row = p.finals ? p.seg[b * 4 + 3] : -1;
+  const int64_t s = start + p.T + p.step, c = start + p.T - 1;  // the predicted frame's episode step; the context's last
+  const uint8_t* ysrc = om_target(p, first, s, len, final_row, pf);
+  const uint8_t* rsrc = ysrc && s >= 1 ? p.frames + (first + s - 1) * pf : nullptr;  // (a valid frame has s <= len)
+  const uint8_t* asrc = ysrc && c >= 0 && c < len ? p.frames + (first + c) * pf : nullptr;
+  const float* pred = p.pred + b * pf;
+  const float* seen = p.ctx_obs + (b * p.T + (p.head + p.T - 1) % p.T) * pf;
+  om_sums acc;
+#pragma unroll
+  for (int k = 0; k < OM_SUMS; ++k) acc.e[k] = 0ull;
+  if (ysrc) {  // uniform over the workgroup
+    if (W == 1) {
+      for (int64_t u = tid; u < pf; u += 256)
+        om_level(ysrc[u], rsrc ? rsrc[u] : 0u, asrc ? asrc[u] : 0u, pred[u], seen[u], acc);
+    } else {
+      constexpr int U = W == 16 ? 4 : 1;  // words in flight per lane
+      const int64_t words = pf >> 2;
+      for (int64_t w0 = 0; w0 < words; w0 += 256 * U) {
+        f32x4 pv[U], mv[U];
+        uint32_t yk[U], rk[U], ak[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+          const int64_t w = w0 + k * 256 + tid;
+          rk[k] = ak[k] = 0u;
+          if (w < words) {
+            pv[k] = *(const f32x4*)(pred + w * 4);
+            mv[k] = *(const f32x4*)(seen + w * 4);
+            yk[k] = *(const uint32_t*)(ysrc + w * 4);
+            if (rsrc) rk[k] = *(const uint32_t*)(rsrc + w * 4);
+            if (asrc) ak[k] = *(const uint32_t*)(asrc + w * 4);
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+          if (w0 + k * 256 + tid < words) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              om_level((yk[k] >> (8 * e)) & 0xff, (rk[k] >> (8 * e)) & 0xff, (ak[k] >> (8 * e)) & 0xff, pv[k][e], mv[k][e], acc);
+          }
+        }
+      }
+    }
+  }
+  // every lane arrives here: wave butterflies, then the four waves in order
+#pragma unroll
+  for (int k = 0; k < OM_SUMS; ++k) acc.e[k] = ol_wave_sum(acc.e[k]);
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < OM_SUMS; ++k) red[tid >> 6][k] = acc.e[k];
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  unsigned long long m[OM_SUMS];
+  for (int k = 0; k < OM_SUMS; ++k) m[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+  if (!rsrc) m[0] = m[2] = m[4] = m[5] = m[6] = 0ull;
+  if (!asrc) m[1] = 0ull;
+  for (int k = 0; k < OM_SUMS; ++k) p.out[b * 8 + k] = (int64_t)m[k];
+  p.out[b * 8 + 7] = 0;
+  p.out_valid[b * 3 + 0] = ysrc ? 1 : 0;
+  p.out_valid[b * 3 + 1] = rsrc ? 1 : 0;
+  p.out_valid[b * 3 + 2] = asrc ? 1 : 0;
+}
+
+extern "C" int dmd_openloop_motion(const dmd_openloop_motion_params* pp, dmd_stream_t stream) {
+  DMD_CHECK_ARG(pp, "openloop_motion: null parameter block");
+  const dmd_openloop_motion_params& p = *pp;
+  DMD_CHECK_ARG(p.frames && p.end && p.seg, "openloop_motion: null arena array or descriptor");
+  DMD_CHECK_ARG(p.pred && p.ctx_obs, "openloop_motion: null prediction or context ring");
+  DMD_CHECK_ARG(p.out && p.out_valid, "openloop_motion: null output");
+  DMD_CHECK_ARG(p.B >= 0 && p.T >= 1 && p.per_frame >= 1 && p.per_frame <= (1ll << 40), "openloop_motion: B %d, T %d, per_frame %lld", p.B, p.T,
+                (long long)p.per_frame);
+  DMD_CHECK_ARG(p.step >= 0 && p.head >= 0 && p.head < p.T, "openloop_motion: step %d (>= 0), head %d of a ring of %d", p.step, p.head, p.T);
+  if (p.B == 0) return 0;
+  const uintptr_t u8_bases = (uintptr_t)p.frames | (uintptr_t)p.finals;
+  const uintptr_t f32_bases = (uintptr_t)p.pred | (uintptr_t)p.ctx_obs;
+  const bool words = p.per_frame % 4 == 0 && u8_bases % 4 == 0 && f32_bases % 16 == 0;  // 4-byte level words, 16-byte fp32 loads
+  const dim3 grid((unsigned)p.B), block(256);
+  if (words && p.per_frame % 16 == 0)
+    hipLaunchKernelGGL(openloop_motion_kernel<16>, grid, block, 0, (hipStream_t)stream, p);
+  else if (words)
+    hipLaunchKernelGGL(openloop_motion_kernel<4>, grid, block, 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(openloop_motion_kernel<1>, grid, block, 0, (hipStream_t)stream, p);
+  DMD_LAUNCH_CHECK();
+  return 0;
+}
+
 // ---- per-frame SSIM of uint8 levels in fp64 (open-loop evaluation's structure metric) -------------------------------------------
 // Wang et al. 2004, 11 x 11 window of weights win[i] * win[j], positions whose window lies inside the frame; the contract and the
 // summation order are stated at dmd_frame_ssim in include/diamond_hip.h.  The window sum is SEPARABLE: a workgroup owns one

@@ -131,6 +131,12 @@ class OpenLoopParams(C.Structure):
                 ("out_valid", C.c_void_p), ("out_levels", C.c_void_p)]
 
 
+class MotionParams(C.Structure):
+    _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("per_frame", C.c_int64), ("step", C.c_int32), ("head", C.c_int32),
+                ("frames", C.c_void_p), ("end", C.c_void_p), ("finals", C.c_void_p), ("seg", C.c_void_p), ("pred", C.c_void_p),
+                ("ctx_obs", C.c_void_p), ("out", C.c_void_p), ("out_valid", C.c_void_p)]
+
+
 SSIM_TAPS = 11
 
 
@@ -164,7 +170,7 @@ EXPORTS = (
     "dmd_pack_conv_weight_f16x2", "dmd_linear", "dmd_attention", "dmd_attention_valid", "dmd_attention_f32", "dmd_attention_f16x2", "dmd_attention_bwd", "dmd_attention_bwd_valid",
     "dmd_attention_bwd_mfma", "dmd_attention_bwd_workspace_floats",
     "dmd_edm_pack_input", "dmd_cond_embed", "dmd_edm_denoised", "dmd_euler_step", "dmd_heun_step", "dmd_quantize_u8", "dmd_reset_state",
-    "dmd_dequant_gather", "dmd_segment_gather", "dmd_record_window", "dmd_openloop_step", "dmd_frame_ssim", "dmd_ssim_workspace_doubles", "dmd_resolve_deaths", "dmd_reset_slots", "dmd_merge_slots", "dmd_merge_slots_bwd", "dmd_nchw_to_nhwc",
+    "dmd_dequant_gather", "dmd_segment_gather", "dmd_record_window", "dmd_openloop_step", "dmd_openloop_motion", "dmd_frame_ssim", "dmd_ssim_workspace_doubles", "dmd_resolve_deaths", "dmd_reset_slots", "dmd_merge_slots", "dmd_merge_slots_bwd", "dmd_nchw_to_nhwc",
     "dmd_nhwc_to_nchw", "dmd_gn_stats", "dmd_gn_stats_valid", "dmd_maxpool2", "dmd_lstm_pointwise", "dmd_lstm_pointwise_bwd", "dmd_lambda_returns", "dmd_categorical_sample", "dmd_rew_end_loss",
     "dmd_maxpool2_bwd", "dmd_gn_bwd_workspace_bytes", "dmd_gn_silu_bwd", "dmd_wgrad_workspace_floats", "dmd_conv2d_wgrad", "dmd_wgrad_job", "dmd_wgrad_reduce_jobs",
     "dmd_conv2d_dgrad_input", "dmd_lowres_chain", "dmd_lowres_chain32", "dmd_last_error", "dmd_abi_version", "dmd_reload_env",
@@ -274,6 +280,7 @@ def declare_signatures(L: C.CDLL) -> None:
     L.dmd_segment_gather.argtypes = [C.POINTER(SegmentGatherParams), C.c_void_p]
     L.dmd_record_window.argtypes = [C.POINTER(RecordWindowParams), C.c_void_p]
     L.dmd_openloop_step.argtypes = [C.POINTER(OpenLoopParams), C.c_void_p]
+    L.dmd_openloop_motion.argtypes = [C.POINTER(MotionParams), C.c_void_p]
     L.dmd_frame_ssim.argtypes = [C.POINTER(SsimParams), C.c_void_p]
     L.dmd_ssim_workspace_doubles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     L.dmd_ssim_workspace_doubles.restype = C.c_int64

@@ -575,6 +575,44 @@ typedef struct dmd_openloop_params {
 } dmd_openloop_params;
 int dmd_openloop_step(const dmd_openloop_params* p, dmd_stream_t stream);
 
+/* ---- open-loop evaluation: what moved in the recording, what the prediction moved, what copying a frame would score -----------
+ * (additive to ABI v11.)  One launch per evaluated step, issued BEFORE that step's dmd_openloop_step: it reads the ring as it
+ * stands before the advance and writes nothing but `out` and `out_valid`.  Arena, descriptor, T, step and head: those of
+ * dmd_openloop_step.  For sample b, with s = start + T + step, in uint8 levels, level(v) = clamp(rint((v + 1) / 2 * 255), 0, 255)
+ * (dmd_quantize_u8's expression, the one device function dmd_openloop_step compares with):
+ *   y   the target by dmd_openloop_step's rule: frames[first + s] when 0 <= s < len; finals[final_row] when s == len, final_row >= 0
+ *       and end[first + len - 1] != 0; otherwise the frame is INVALID: all eight outputs and all three flags are 0
+ *   r   the previous recorded frame, frames[first + s - 1]; valid when the frame is valid and s >= 1
+ *   a   the anchor, the context's last frame, frames[first + start + T - 1]; valid when the frame is valid and 0 <= start + T - 1 < len
+ *   q   level(pred[b])
+ *   m   level(ctx_obs[b][(head + T - 1) % T]): the ring's NEWEST slot, the frame the model itself saw last (free running from step 1
+ *       on: its own previous prediction; at step 0 or teacher forced: the recording).  No other slot of the ring is read.
+ *   out[b] = { sum (y - r)^2,  sum (y - a)^2,  #{y != r},  #{q != m},  #{y != r and q != m},  sum over {y != r} of (q - y)^2,
+ *              #{y != r and q == y},  0 }
+ *            entries 0, 2, 4, 5, 6 are 0 where r is not valid, entry 1 is 0 where a is not valid, entry 3 counts every valid frame.
+ *   out_valid[b] = { frame valid, r valid, a valid }
+ * Exact integers, 64-bit from the lane's partial sum to `out` (a 256 x 256 x 3 frame exceeds 2^32 in entries 0, 1 and 5).  Nothing
+ * outside the episode is read (never an out-of-range address); r and a are not read where they are not valid, an invalid frame
+ * reads neither pred nor the ring.  One workgroup per sample; the sums are reduced in a fixed order (and are integers).  Any
+ * per_frame >= 1: 16-byte loads of pred / ctx_obs where per_frame % 4 == 0 and the pointers are aligned (pred / ctx_obs 16 bytes,
+ * frames / finals 4; 16 levels per lane and pass where per_frame % 16 == 0, else 4); one level per lane otherwise.
+ * Refused (non-zero, dmd_last_error): NULL frames / end / seg / pred / ctx_obs / out / out_valid; B < 0, T < 1, per_frame < 1,
+ * step < 0, head outside [0, T).  finals may be NULL (final_row is then never followed).  B == 0 returns 0 and launches nothing. */
+typedef struct dmd_openloop_motion_params {
+  int32_t B, T;
+  int64_t per_frame;       /* C * H * W */
+  int32_t step, head;      /* as dmd_openloop_params: the evaluated step, the ring's OLDEST slot (where that step's frame will go) */
+  const uint8_t* frames;   /* (F, per_frame) */
+  const uint8_t* end;      /* (F) */
+  const uint8_t* finals;   /* (E, per_frame) or NULL */
+  const int64_t* seg;      /* (B, 4): first, start, len, final_row */
+  const float* pred;       /* (B, per_frame) */
+  const float* ctx_obs;    /* (B, T, per_frame) ring BEFORE the advance */
+  int64_t* out;            /* (B, 8) */
+  uint8_t* out_valid;      /* (B, 3): frame, previous, anchor */
+} dmd_openloop_motion_params;
+int dmd_openloop_motion(const dmd_openloop_motion_params* p, dmd_stream_t stream);
+
 /* ---- per-frame SSIM of uint8 levels, in fp64, on the device ---------------------------------------------------------------------
  * (additive to ABI v11.)  Wang et al. 2004 as the common implementations compute it: operands are levels 0 ... 255 as fp64, a
  * window of 11 taps per axis with weight win[i] * win[j] at tap (i, j), and only the positions whose window lies wholly inside the

@@ -18,6 +18,10 @@ Prints one JSON line and writes it to profiles/openloop_eval.json.  Needs the GP
 (one dmd_frame_ssim call per step more) in the same alternating blocks, the entry point's own time from a replayed graph of
 `--ssim-graph-calls` arena-mode calls, and its largest difference from the 121-tap numpy restatement (tests/ssim_cases.py) over
 the GPU tests' production shapes.  Writes profiles/openloop_ssim.json.
+
+`--motion`: the same for `open_loop_eval(..., motion=True)` -- arm `motion_off` against arm `motion_on` (one dmd_openloop_motion
+launch per step more) in the same alternating blocks, and the entry point's own time from a replayed graph of `--ssim-graph-calls`
+calls.  Writes profiles/openloop_motion.json.
 """
 import argparse
 import json
@@ -159,6 +163,81 @@ def ssim_arms(args, sampler, agent, store, ids, t):
     return 0
 
 
+def motion_arms(args, sampler, agent, store, ids, t):
+    import ctypes
+
+    from diamond_amd import native as nv
+    from diamond_amd.openloop import MOTION_FIELDS, open_loop_eval
+
+    dev, b, horizon, tf = store.device, args.batch, args.horizon, args.teacher_forced
+    arms = {"motion_off": lambda: open_loop_eval(sampler, agent.rew_end_model, store, ids, horizon, teacher_forced=tf),
+            "motion_on": lambda: open_loop_eval(sampler, agent.rew_end_model, store, ids, horizon, teacher_forced=tf, motion=True)}
+    noise = torch.randn(horizon, b, *FRAME, device=dev)
+    reports = {}
+    for name, fn in arms.items():  # the same injected draws: motion changes no other field
+        left = list(noise)
+        sampler.noise_fn = lambda shape, d: left.pop()
+        reports[name] = fn()
+    sampler.noise_fn = None
+    same = all(torch.equal(getattr(reports["motion_on"], k), getattr(reports["motion_off"], k)) for k in
+               ("sq_err", "abs_err", "max_err", "pixels_off", "frame_valid", "transition_valid", "logits_rew", "logits_end", "ctx_obs"))
+    sm = reports["motion_on"].summary()
+    for fn in arms.values():
+        fn()
+    torch.cuda.synchronize()
+    ms = blocks_ms(arms, args.blocks, args.evals)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    spread = {k: max(v) - min(v) for k, v in ms.items()}
+
+    # the entry point alone: a graph of calls on a prediction-shaped operand and a ring, replayed
+    seg = torch.from_numpy(store._descriptor(ids)[0]).to(dev)
+    pred = torch.rand((b,) + FRAME, device=dev) * 2 - 1
+    ring = torch.rand((b, t) + FRAME, device=dev) * 2 - 1
+    out, valid = torch.empty((b, 8), dtype=torch.int64, device=dev), torch.empty((b, 3), dtype=torch.uint8, device=dev)
+    p = nv.MotionParams()
+    p.B, p.T, p.per_frame, p.step, p.head = b, t, store.per_frame, 0, 0
+    p.frames, p.end, p.finals, p.seg = (nv.ptr(x) for x in (store.frames, store.end, store.finals, seg))
+    p.pred, p.ctx_obs, p.out, p.out_valid = nv.fptr(pred), nv.fptr(ring), nv.ptr(out), nv.ptr(valid)
+    call = lambda: nv.check(nv.lib().dmd_openloop_motion(ctypes.byref(p), nv.stream()), "dmd_openloop_motion")
+    call()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(args.ssim_graph_calls):
+            call()
+    graph.replay()
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(args.blocks):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        graph.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        us.append(e0.elapsed_time(e1) * 1000.0 / args.ssim_graph_calls)
+    nbytes = int(valid[:, 0].sum()) * store.per_frame * 9 + int(valid[:, 1].sum()) * store.per_frame + int(valid[:, 2].sum()) * store.per_frame
+
+    diff = med["motion_on"] - med["motion_off"]
+    line = {"what": "open_loop_eval(motion=True) against motion=False of the same tree, ms per evaluation (HIP events around alternating blocks)",
+            "device": torch.cuda.get_device_name(0), "batch": b, "horizon": horizon, "context": t, "frame": list(FRAME),
+            "denoising_steps": args.denoising_steps, "teacher_forced": tf, "evals_per_block": args.evals, "blocks_per_arm": args.blocks,
+            "other_fields_agree_bitwise": bool(same), "median_ms": {k: round(v, 4) for k, v in med.items()},
+            "spread_ms": {k: round(v, 4) for k, v in spread.items()}, "blocks_ms": {k: [round(x, 4) for x in v] for k, v in ms.items()},
+            "motion_on_minus_off_ms": round(diff, 4), "increase_exceeds_larger_spread": bool(diff > max(spread.values())),
+            "openloop_motion_call_us_graph_replay": {"calls_per_graph": args.ssim_graph_calls, "median": round(statistics.median(us), 3),
+                                                     "blocks": [round(x, 3) for x in us], "bytes_read_per_call": nbytes,
+                                                     "note": "the same buffers every call: they stay in the caches, not an HBM figure"},
+            "openloop_motion_calls_per_evaluation": horizon,
+            "summary": {k: sm[k] for k in ("skill_prev", "skill_anchor", "change_recall", "change_precision", "share_changed")},
+            "report_fields": list(MOTION_FIELDS)}
+    text = json.dumps(line)
+    print(text, flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch", type=int, default=32)
@@ -171,13 +250,14 @@ def main():
     ap.add_argument("--teacher-forced", action="store_true")
     ap.add_argument("--no-kernel-trace", action="store_true", help="count the C-ABI launches only (no torch.profiler pass)")
     ap.add_argument("--ssim", action="store_true", help="time open_loop_eval(ssim=True) against ssim=False instead")
-    ap.add_argument("--ssim-graph-calls", type=int, default=200, help="dmd_frame_ssim calls in the replayed graph")
+    ap.add_argument("--motion", action="store_true", help="time open_loop_eval(motion=True) against motion=False instead")
+    ap.add_argument("--ssim-graph-calls", type=int, default=200, help="dmd_frame_ssim / dmd_openloop_motion calls in the replayed graph")
     ap.add_argument("--interpreter-max-diff", type=float, default=None,
                     help="recorded as given: the largest difference tests/test_ssim_simt.py printed (pytest -s)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "openloop_ssim.json" if args.ssim else "openloop_eval.json")
+        args.out = os.path.join(ROOT, "profiles", "openloop_ssim.json" if args.ssim else "openloop_motion.json" if args.motion else "openloop_eval.json")
     if not torch.cuda.is_available():
         sys.exit("openloop_bench: no GPU visible -- NOT measured (a time exists on the device only)")
 
@@ -220,6 +300,8 @@ def main():
 
     if args.ssim:
         return ssim_arms(args, sampler, agent, store, ids, t)
+    if args.motion:
+        return motion_arms(args, sampler, agent, store, ids, t)
 
     arms = make_arms(horizon)
 
